@@ -13,11 +13,18 @@ already resident in HBM when the timed region starts.  With N GPUs each rank
 solves its own 4096 realisations (weak scaling) and the recovered channels are
 gathered to rank 0 over RCCL inside the timed region.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode MODE]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode MODE] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line of its mode (with the
+live per-kernel event timing that rides inside the timed steps).  ``--full`` adds every measurement
+that takes runs of its own: the CPU baselines and, on the default line, regime P, the reference's
+refinement input and configs 3 / 4 / 5 and the pipeline (each can be dropped again with its
+``--no-...`` switch).  ``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as DIR/<name>.npy (float64; see dump_outputs).
 
 Modes (each its own line; only ``unit`` is the headline metric):
-  unit       configs[1] (default; ``--variant A2nuclear`` = configs[2]); also measures regime P
-             (private codebooks) and the unit on the reference's own refinement input
+  unit       configs[1] (default; ``--variant A2nuclear`` = configs[2]); with ``--full`` also measures
+             regime P (private codebooks) and the unit on the reference's own refinement input
              (X0 = the pipeline's X_max, inferLowRankV4_multi.m:90-92)
   config5    configs[4]: 32-ant multiresolution codebook, A2nuclear, 65 536 realisations in
              total sharded over the ranks (strong scaling), one RCCL gather
@@ -51,6 +58,8 @@ PROF_STRIDE = 7           # unit mode: kernel events on every 7th launch of each
                           # class and stream over 3 steps; 200 mod 7 != 0, so the sampled iteration indices
                           # drift over the steps; the event pairs cost < 1 % of the throughput)
 CONFIG5_GLOBAL = 65536    # configs[4]: realisations over all GPUs
+DUMP_BUDGET = 48 << 20    # --dump-outputs: bytes over all the arrays of one dump (float64)
+DUMP_SEED = 58659179      # --dump-outputs: seed of the batch-row sample of a dump over the budget
 ITER_CLASSES = ("pre", "apply_A", "apply_G", "ystep", "apply_K", "apply_AH", "zstep")
 
 
@@ -80,12 +89,49 @@ def parse():
     ap.add_argument("--no-prof", action="store_true", help="disable live per-kernel event timing")
     ap.add_argument("--mode", default="unit",
                     choices=["unit", "config5", "pipeline", "phaselift", "beamformer", "driver", "refine"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: CPU baselines, regime P, the "
+                         "refinement input and the other configs of the default line (off: the mode's own line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float64)")
     a = ap.parse_args()
+    if a.dump_outputs and a.mode in ("driver", "refine"):
+        ap.error(f"--dump-outputs is not available in --mode {a.mode}")
+    if not a.full:
+        a.no_cpu_baseline = a.no_regime_p = a.no_refine_input = a.no_configs = True
     if not a.tx:
         a.tx = 16 if a.mode in ("beamformer", "driver") else 32
     if not a.batch:
         a.batch = {"phaselift": 512, "beamformer": 65536}.get(a.mode, 4096)
     return a
+
+
+# ------------------------------------------------------------------ output dump
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays {name: [batch, ...]} the last timed step returned (torch tensors or
+    numpy arrays), each as <path>/<name>.npy in float64 (complex as a trailing [re, im] axis, integers
+    converted).  When they exceed DUMP_BUDGET bytes together, every array keeps the same sample of
+    the batch rows, drawn once from DUMP_SEED (ascending)."""
+    import torch
+    path = pathlib.Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    batch = next(iter(arrays.values())).shape[0]
+    row_bytes = 0
+    for v in arrays.values():
+        cplx = v.is_complex() if isinstance(v, torch.Tensor) else np.iscomplexobj(v)
+        row_bytes += (16 if cplx else 8) * int(np.prod(v.shape[1:], dtype=np.int64))
+    keep = max(1, min(batch, DUMP_BUDGET // row_bytes))
+    rows = None if keep == batch else np.sort(np.random.default_rng(DUMP_SEED).choice(batch, keep, replace=False))
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            if rows is not None:
+                v = v[torch.from_numpy(rows).to(v.device)]
+            v = v.detach().cpu().numpy()
+        elif rows is not None:
+            v = v[rows]
+        v = np.stack([v.real, v.imag], axis=-1) if np.iscomplexobj(v) else v
+        np.save(path / f"{name}.npy", np.ascontiguousarray(v, dtype=np.float64))
 
 
 # ------------------------------------------------------------------ roofline accounting
@@ -439,8 +485,9 @@ def _work_accounting(per_gpu, variant, m, n, tx, iters, msp_frac):
     return d
 
 
-def unit_bench(args, private, dev, rank, world, workload=None):
+def unit_bench(args, private, dev, rank, world, workload=None, dump=None):
     """One unit-metric measurement (regime S or P, or a given workload); the JSON line dict on rank 0.
+    dump: directory for the last timed step's outputs (dump_outputs; the mode's own line only).
     workload: {"tag", "name", "variant", "A" (device codebook), "A_host", "bsz", "first", "counts",
     "scaling", "codebook", "X0" (device X0), "x0_note"} -- all optional."""
     import torch
@@ -516,6 +563,8 @@ def unit_bench(args, private, dev, rank, world, workload=None):
     finite = bool(torch.isfinite(torch.view_as_real(out.X)).all().item())
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, {"X": out.X, "Y": out.Y, "iters": out.iters, "status": out.status, "mu": out.mu})
 
     total = sum(counts) * args.steps
     kernels, roof, roof_gemm, roof_msr = {}, None, None, None
@@ -795,6 +844,9 @@ def bench_pipeline(args, dev, rank, world):
     elapsed = _max_over_ranks(elapsed, dev, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"X": res.X, "Y": res.Y, "quality": res.quality,
+                                         "stage_iters": res.stage_iters, "status": res.status})
     its = res.stage_iters.cpu().numpy()
     Xh = res.X.cpu().numpy()
     Hh = H.cpu().numpy()
@@ -883,6 +935,8 @@ def bench_phaselift(args, dev, rank, world):
     elapsed = _max_over_ranks(elapsed, dev, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sig": res.sig, "iters": res.iters, "status": res.status})
     its = res.iters.cpu().numpy()
     names = {"setup": "setup (reduction)", "pre": "y, A_y, gradient", "apply_AH": "A*(g) GEMM",
              "zstep": "prox eig (tridiag+bisect+invit+backxf)", "apply_G": "prox assembly GEMM",
@@ -971,6 +1025,9 @@ def bench_beamformer(args, dev, rank, world):
     elapsed = _max_over_ranks(elapsed, dev, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"wr_code": res.wr_code, "wt_code": res.wt_code, "beam_idx": res.beam_idx,
+                                         "rss": res.rss, "status": res.status})
     st = res.status.cpu().numpy()
     per_unit = 16.0 * tx * tx + 2 * tx + 8 + 8 + 4        # read H; write codes, idx, rss, status
     achieved = per_unit * bsz / (kern_ms * 1e-3) / 1e9
@@ -1141,11 +1198,11 @@ def config_legs(args, dev, rank, world):
         return _leg_summary(ln, ("kernels_ms", "checks")) if rank == 0 else None
 
     def config4():
-        a = _sub(args, batch=512, steps=1, warmup=1, cpu_seconds=cpu_s)
+        a = _sub(args, batch=512, steps=1, warmup=1, cpu_seconds=cpu_s, dump_outputs=None)
         return _leg_summary(bench_phaselift(a, dev, rank, world), ("iters_all", "device_time_shares"))
 
     def pipeline():
-        a = _sub(args, batch=4096, steps=1, warmup=1, cpu_seconds=cpu_s, cpu_recoveries=2)
+        a = _sub(args, batch=4096, steps=1, warmup=1, cpu_seconds=cpu_s, cpu_recoveries=2, dump_outputs=None)
         return _leg_summary(bench_pipeline(a, dev, rank, world), ("stage_iters_mean", "device_time_shares"))
 
     return [("config3", config3), ("config5_shard", config5), ("config4", config4), ("pipeline", pipeline)]
@@ -1180,11 +1237,12 @@ def main():
                               "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
                               "dtype": "f64", **ri}), flush=True)
     elif args.mode == "config5":
-        line = unit_bench(args, False, dev, rank, world, config5_workload(args, rank, world, dev))
+        line = unit_bench(args, False, dev, rank, world, config5_workload(args, rank, world, dev),
+                          dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(line), flush=True)
     else:
-        line = unit_bench(args, args.private, dev, rank, world)
+        line = unit_bench(args, args.private, dev, rank, world, dump=args.dump_outputs)
         if not args.private and args.variant == "A2only":
             # The secondary measurements ride on the headline line; a failure in one of them is reported
             # in its own field ({"error": ...}, the traceback on stderr) instead of discarding the

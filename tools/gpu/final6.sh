@@ -10,6 +10,6 @@ echo "== smoke $(date +%T)"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1 || { tail -20 $O/${T}_smoke.log; exit 1; }
 tail -2 $O/${T}_smoke.log
 echo "== bench $(date +%T)"
-timeout -k 10 900 python -u bench.py > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err || { tail -20 $O/${T}_bench_default.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/${T}_bench_default.json').read().strip().splitlines()[-1]); print(d['metric'], d['value']); [print(k, v.get('value') if isinstance(v, dict) else v) for k, v in d.items() if k.startswith('config') or k == 'pipeline']"
 echo "== done $(date +%T)"

@@ -14,7 +14,7 @@ pmc() { local tag=$1 cnt=$2; shift 2; echo "== pmc $tag $cnt $(date +%T)"; timeo
 pmc pipeline FETCH_SIZE --mode pipeline --steps 1 --warmup 0
 pmc pipeline WRITE_SIZE --mode pipeline --steps 1 --warmup 0
 python3 tools/pmc_summary.py $O/pipeline_FETCH_SIZE/run_counter_collection.csv $O/pipeline_WRITE_SIZE/run_counter_collection.csv profiles/${R}_pipeline_pmc_hbm.json > $O/pipeline_pmc.txt && cp profiles/${R}_pipeline_pmc_hbm.json $O/
-run() { local tag=$1; shift; echo "== $tag $(date +%T)"; timeout -k 10 600 python -u bench.py "$@" > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }; cut -c1-200 $O/$tag.json; }
+run() { local tag=$1; shift; echo "== $tag $(date +%T)"; timeout -k 10 600 python -u bench.py --full "$@" > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }; cut -c1-200 $O/$tag.json; }
 run unit
 run nuclear --variant A2nuclear --steps 5
 run config5 --mode config5 --steps 3

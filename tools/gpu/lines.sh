@@ -18,7 +18,7 @@ for l in "$@"; do
     *) echo "unknown line $l"; exit 2;;
   esac
   echo "== $l $(date +%T)"
-  timeout -k 10 900 python3 -u bench.py $a > $O/$l.json 2> $O/$l.err || { tail -20 $O/$l.err; exit 1; }
+  timeout -k 10 900 python3 -u bench.py --full $a > $O/$l.json 2> $O/$l.err || { tail -20 $O/$l.err; exit 1; }
   cut -c1-300 $O/$l.json
 done
 echo "== done $(date +%T)"
