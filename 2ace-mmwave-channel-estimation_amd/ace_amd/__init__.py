@@ -15,6 +15,7 @@ from .pipeline import (inferLowRankV4_multi, inferLowRankV4, inferLowRank_Nuclea
 from .phaselift import MyPhaseLift, phaselift_host, phaselift_batch, PhaseLiftResult, prox_eig_host  # noqa: F401
 from .beamformer import (svd_beamformer, svd_beamformer_compensation, codebook_beams,  # noqa: F401
                          svd_beamformer_host, svd_beamformer_batch, BeamResult)
-from . import synth, engine  # noqa: F401
+from .evaluate import evaluate_host, evaluate_batch, EvalResult  # noqa: F401
+from . import synth, engine, montecarlo  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

@@ -1,0 +1,84 @@
+"""Monte-Carlo sweep over the number of measurements: the reference's ``Vs_M`` loop
+(Numerical_Simulation/Vs_M.m:163-226: synthesise, recover, ``Evaluation_H``, average) for the two
+ADMM methods, with every step on the GPU.
+
+Per sweep point M: a shared phase-code codebook and the channels from the device synth
+(``solver.synth_problem``), the recovery pipeline on per-realisation train partitions
+(``pipeline.infer_low_rank_pipeline_batch``) and ``evaluate.evaluate_batch`` against the synthesised
+vec(H).  Only the [count][4] metrics and the status words leave the device.
+
+Shards.  The pipeline's results depend, at rounding level, on the batch a realisation is solved in: its
+r-column stages take the int8 digit-plane applies from 256 vectors (batch x r) on and f64 GEMMs below, and
+the rank-one retry solves the failing realisations as a sub-batch of their own.  The sweep
+therefore always solves whole chunks of ``chunk`` consecutive realisations on the grid of the sweep's own
+realisation index (realisation i belongs to chunk i // chunk, whatever ``first`` and ``count``), and keeps
+the rows asked for: a realisation's metrics are a function of (seed, M, i, chunk) alone, and any shard
+reproduces its rows of the full run bit for bit.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from ._lib import pipeline_cfg, ACE_ST_EVAL_DEGENERATE
+from .evaluate import METRICS, evaluate_batch
+
+METHODS = ("A2only", "A2nuclear")
+CHUNK = 64   # realisations per pipeline call (the default of vs_m's ``chunk``)
+
+
+def vs_m(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, first=0, maxiter=None,
+         device=None, chunk=CHUNK) -> dict:
+    """Evaluation_H metrics of ``count`` recoveries at each M of ``M_list``.
+
+    Realisation b of the call is realisation ``first + b`` of the sweep: its channel, its noise and its
+    train partitions (the build's counter RNG, seed ``seed``, stream ``(first + b) * restarts + restart``:
+    what the pipeline draws for ``train_idx = NULL`` on a batch that starts at realisation 0) depend on that
+    index alone, and the codebook of a sweep point on ``seed`` and M, so shards of a sweep compose (see the
+    module text for ``chunk``; a call whose range is not chunk-aligned solves up to ``chunk - 1`` extra
+    realisations at each end and drops them on the device).  ``maxiter`` caps every ADMM stage (default: the
+    reference's 500).
+
+    Returns a dict: ``M`` [nM], ``metrics`` [nM][count][4] (columns ``evaluate.METRICS``), ``status``
+    [nM][count] (the evaluator's), ``mean`` [nM][4] (the reference's
+    mean(Evaluation) over the realisations, degenerate ones included with nmse = proj_err = 1 and zero
+    gains) and ``n_degenerate`` [nM].  A sweep point the pipeline refuses (e.g. floor(0.95 M) < min(20, M)
+    train rows) raises the pipeline's own error (AceError, or the ValueError of
+    ``infer_low_rank_pipeline_batch`` for a configuration its workspace query rejects); it is not masked."""
+    import torch
+    from .engine import randperm
+    from .pipeline import infer_low_rank_pipeline_batch
+    from .solver import VARIANTS, synth_problem
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if tx != rx:
+        # the synth vectorises its Nr x Nt channel with rx leading (k = r + rx t, Generate_Channel.m), the
+        # pipeline and the evaluator read n-vectors with tx leading (k = i + tx j): the two agree for square arrays
+        raise ValueError(f"vs_m needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    count, first, chunk = int(count), int(first), int(chunk)
+    if count < 1 or first < 0 or chunk < 1:
+        raise ValueError("count and chunk must be >= 1 and first >= 0")
+    Ms = [int(M) for M in M_list]
+    dev = torch.device("cuda" if device is None else device)
+    cfg = pipeline_cfg(VARIANTS[method])
+    R = cfg.restarts
+    kw = {} if maxiter is None else {"maxiter": int(maxiter)}
+    metrics = np.empty((len(Ms), count, 4), np.float64)
+    status = np.empty((len(Ms), count), np.uint32)
+    end = first + count
+    for k, M in enumerate(Ms):
+        mt = math.floor(M * cfg.cc_frac)
+        for c0 in range(first // chunk * chunk, end, chunk):
+            A, B, _, H = synth_problem(seed, c0, chunk, M, tx, rx, L=L, snr_db=snr_db, device=dev)
+            tr = np.stack([np.stack([randperm(seed, (c0 + b) * R + i, M, mt) for i in range(R)])
+                           for b in range(chunk)])
+            rec = infer_low_rank_pipeline_batch(A, B, tx, rx, tr, variant=method, restarts=R, **kw)
+            ev = evaluate_batch(rec.X, H, tx, rx)
+            lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+            rows = slice(lo - first, hi - first)
+            metrics[k, rows] = ev.metrics[lo - c0:hi - c0].cpu().numpy()
+            status[k, rows] = ev.status[lo - c0:hi - c0].cpu().numpy().view(np.uint32)
+    return {"M": np.asarray(Ms, np.int64), "metrics": metrics, "status": status,
+            "mean": metrics.mean(axis=1), "n_degenerate": ((status & ACE_ST_EVAL_DEGENERATE) != 0).sum(axis=1),
+            "columns": METRICS}

@@ -311,6 +311,30 @@ int ace_svd_beamformer_host(int batch, int tx, int rx, const double* H, const do
                             uint8_t* wr_code, uint8_t* wt_code, int32_t* beam_idx, double* rss,
                             uint32_t* status, double* vh_r, double* vh_t);
 
+/* ---- channel evaluation (the reference's parity metric) ----------------------
+ * Evaluation_H (Numerical_Simulation/src/evaluate_plot_results/Evaluation_H.m:73-132), batched.
+ * X, G: [batch][n] c128 DEVICE (n = tx*rx, vec(H) order); metrics: [batch][4] f64 DEVICE
+ * = {nmse, gain_ana, gain_dig, proj_err}; status [batch] (may be NULL).  Asynchronous on stream.
+ *   nmse     = ||g - ((x^H g)/(x^H x)) x||^2 / ||g||^2                         (:87-89)
+ *   gain_ana = |Q(u1)^H mat(g) Q(v1)|, Q = Quantize_PS at 2 bits                (:95-99, :103)
+ *   gain_dig = |u1^H mat(g) v1| with unit u1, v1                                (:100-104)
+ *   proj_err = ||X_g - ((X^H X_g)/(X^H X)) X|| / ||X_g||, X / X_g the rank-one parts of
+ *              mat(x) / mat(g)                                                  (:107-115)
+ * u1, v1 are the top singular vectors of mat(x) (tx x rx, entry (i, j) = x[i + tx*j]) in the gauge
+ * of ace_svd_beamformer_batch: v1 = conj(row 0 of vh_r), u1 = row 0 of vh_t.  gain_ana is invariant
+ * under powers of j on u1 or v1, so the divide-and-conquer sign (ACE_ST_BF_DC) does not reach it;
+ * the other metrics are gauge-free.  1 <= tx, rx <= 32, batch >= 1; bad shapes and NULL X, G or
+ * metrics return ACE_ERR_ARG before any HIP call.
+ * Departure from the reference: an x or g that is all zero or not finite (where the reference
+ * returns NaN or an arbitrary basis vector) gives nmse = 1, proj_err = 1, both gains 0 and
+ * ACE_ST_EVAL_DEGENERATE, so Monte-Carlo means stay finite and the flag can be counted.
+ * ACE_ST_BF_NOCONV: an SVD exhausted its iteration budget. */
+#define ACE_ST_EVAL_DEGENERATE 256u
+int ace_evaluate_batch(int batch, int tx, int rx, const double* X, const double* G,
+                       double* metrics, uint32_t* status, void* stream);
+int ace_evaluate_host(int batch, int tx, int rx, const double* X, const double* G,
+                      double* metrics, uint32_t* status);   /* allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
