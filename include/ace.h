@@ -248,6 +248,59 @@ int ace_phaselift_solve_host_x(const ace_phaselift_cfg* cfg, int batch, int m, i
 int ace_prox_eig_host(int batch, int d, int path, const double* A, const double* tau, double* lam, double* V,
                       int32_t* k);
 
+/* ---- test entries: one application of a linear operator of the ADMM iteration ---------------
+ * The four operators every solver loops around, on their own (tests/test_gpu_linops.py compares them with
+ * exact references):
+ *   ACE_LINOP_A      T  = (Y - M/mu) - A (Z - N/mu)
+ *   ACE_LINOP_AH     X  = (Z - N/mu) + A^H g     (ACE_LINOP_I8 at rcols = 1: W = A^H g alone, as the Z-step takes it)
+ *   ACE_LINOP_K      KY = K g,  K = A A^H        (the operand is passed in `g`)
+ *   ACE_LINOP_G      g' = G g,  G = (I + K)^-1   (the operand is passed in `g`; f64 only)
+ *   ACE_LINOP_SETUP  no application: out = K, out2 = G ([1 | batch][m][m] c128) and out3 = {c, c^2} (the
+ *                    phase-code scale; zeros unless path = ACE_LINOP_I8) as the operator setup left them
+ * The entry builds the operators with the solver's own setup, fills one control block per realisation from
+ * mu / vbound / done / nzero / avok (every other field zero) and makes the launcher calls a solve makes for the
+ * operator on the chosen path:
+ *   ACE_LINOP_F64        a_shared: the pre-pass (V = Z - N/mu, S = Y - M/mu) and the 3M matrix-core GEMM;
+ *                        private codebooks (a_shared = 0, rcols = 1): the pre-pass and the GEMV kernels
+ *   ACE_LINOP_F64_FUSED  shared A, rcols = 1, A / AH: the GEMM with the pre-pass folded in
+ *   ACE_LINOP_I8         shared phase-code A: the exact int8 digit planes (rcols = 1: the unit path's launches;
+ *                        rcols > 1: the r-column stages', vector j of realisation j / rcols).  ACE_ERR_UNSUPPORTED
+ *                        when the setup does not take the codebook (no fall-back to f64).
+ * All arrays are HOST, row-major c128 as (re, im) doubles: A [1 | batch][m][n]; Z, N [batch * rcols][n];
+ * Y, M, g, AX [batch * rcols][m]; mu, vbound, done, nzero, avok [batch].  N, M (NULL: zero), vbound (NULL: 0), the
+ * flags (NULL: 0) and AX (int8 apply_A at rcols = 1 only: the A V of realisations with avok) are optional.
+ * out ([batch * rcols][m], AH: [..][n]) is filled with `sentinel` before the launch, so rows a kernel leaves
+ * alone (done realisations) show.  The fused kernels that carry solver state (the g / Y-step / K Y kernels, the
+ * private code-image kernel, apply_AH's fused Z-step) are not reachable from here.
+ * Synchronous; allocates its own device memory. */
+#define ACE_LINOP_A 0
+#define ACE_LINOP_AH 1
+#define ACE_LINOP_K 2
+#define ACE_LINOP_G 3
+#define ACE_LINOP_SETUP 4
+#define ACE_LINOP_F64 0
+#define ACE_LINOP_F64_FUSED 1
+#define ACE_LINOP_I8 2
+typedef struct ace_linop_args {
+    int op, path, a_shared, batch, m, n, rcols, reserved;
+    const double* A;
+    const double *Z, *N, *Y, *M, *g, *AX;
+    const double *mu, *vbound;
+    const int32_t *done, *nzero, *avok;
+    double sentinel;
+    double *out, *out2, *out3;
+} ace_linop_args;
+int ace_linop_host(const ace_linop_args* args);
+/* The f64 3M matrix-core GEMM launcher with all of its arguments (test entry):
+ *   C[z][b][i] = epi( sum_k op(L[z])[i][k] V[z][b][k] ),  mode 0: acc, 1: E - acc, 2: E + acc;  conj_l: op = conj.
+ * L, V, C, E: HOST c128 arrays of nL, nV, nC, nC complex elements with leading dimensions ldl, ldv, ldc and z strides
+ * (complex elements); C is uploaded as given (a caller's sentinel shows what the kernel wrote) and read back.  klim
+ * (optional, nklim doubles): per z-slice bound on k, read from klim[z * klim_stride]; the operands must be zero at
+ * and beyond it.  ACE_ERR_ARG when an operand extent exceeds its array.  Synchronous. */
+int ace_zgemm_host(int mode, int conj_l, int M, int K, int nb, const double* L, long long nL, int ldl, long long strideL,
+                   const double* V, long long nV, int ldv, long long strideV, double* C, const double* E, long long nC,
+                   int ldc, long long strideC, int nz, const double* klim, long long nklim, long long klim_stride);
+
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(
  *                         tx_ant_num, rx_ant_num, cb_amp, cb_angle, rss_final, seed_id)

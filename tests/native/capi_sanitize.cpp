@@ -106,6 +106,26 @@ void host_only() {
     CHECK(ace_recover_driver(0, 4, 4, 8, nullptr, &d, &d, 1, 0, nullptr, &d, &d) == ACE_ERR_ARG);
     CHECK(strlen(ace_last_error()) > 0);
     CHECK(strlen(ace_version()) > 0);
+    // the operator test entries: argument and extent checks
+    CHECK(ace_linop_host(nullptr) == ACE_ERR_ARG);
+    ace_linop_args la{};
+    la.op = 9;
+    CHECK(ace_linop_host(&la) == ACE_ERR_ARG);
+    la.op = ACE_LINOP_A;
+    la.path = ACE_LINOP_I8;
+    la.a_shared = 1;
+    la.batch = la.m = la.n = la.rcols = 1;
+    CHECK(ace_linop_host(&la) == ACE_ERR_ARG);   // NULL A / out / mu
+    la.A = la.mu = &d;
+    la.out = &d;
+    la.rcols = 0;
+    CHECK(ace_linop_host(&la) == ACE_ERR_ARG);
+    la.rcols = 2;
+    la.path = ACE_LINOP_F64_FUSED;
+    CHECK(ace_linop_host(&la) == ACE_ERR_UNSUPPORTED);   // the fused GEMMs run at rcols = 1
+    CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 3, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
+    CHECK(ace_zgemm_host(1, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
+    CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 1, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
 }
 
 void gpu_solves() {
@@ -187,6 +207,57 @@ void gpu_solves() {
                                      hg.data()) == 2);
             CHECK(finite(ha) && finite(hg));
         }
+    }
+    // ---- operator test entries: T = (Y - M/mu) - A (Z - N/mu) on every path, the setup read-back, one raw GEMM
+    {
+        const auto Z = cvec((size_t)batch * n), Nn = cvec((size_t)batch * n), Y = cvec((size_t)batch * m),
+                   Mm = cvec((size_t)batch * m);
+        const std::vector<double> mu(batch, 1.5), vb(batch, 2.0);
+        const std::vector<int32_t> done = {0, 1, 0};
+        for (int path : {ACE_LINOP_F64, ACE_LINOP_F64_FUSED, ACE_LINOP_I8}) {
+            std::vector<double> T(2 * (size_t)batch * m);
+            ace_linop_args la{};
+            la.op = ACE_LINOP_A;
+            la.path = path;
+            la.a_shared = 1;
+            la.batch = batch;
+            la.m = m;
+            la.n = n;
+            la.rcols = 1;
+            la.A = A.data();
+            la.Z = Z.data();
+            la.N = Nn.data();
+            la.Y = Y.data();
+            la.M = Mm.data();
+            la.mu = mu.data();
+            la.vbound = vb.data();
+            la.done = done.data();
+            la.sentinel = -3.0;
+            la.out = T.data();
+            CHECK(ace_linop_host(&la) == ACE_OK);
+            CHECK(finite(T));
+            if (path != ACE_LINOP_F64) CHECK(T[2 * (size_t)m] == -3.0 && T[0] != -3.0);   // the done row is left alone
+        }
+        std::vector<double> K(2 * (size_t)m * m), G(2 * (size_t)m * m), c(2);
+        ace_linop_args ls{};
+        ls.op = ACE_LINOP_SETUP;
+        ls.path = ACE_LINOP_I8;
+        ls.a_shared = 1;
+        ls.batch = 1;
+        ls.m = m;
+        ls.n = n;
+        ls.rcols = 1;
+        ls.A = A.data();
+        ls.mu = mu.data();
+        ls.out = K.data();
+        ls.out2 = G.data();
+        ls.out3 = c.data();
+        CHECK(ace_linop_host(&ls) == ACE_OK);
+        CHECK(finite(K) && finite(G) && c[0] == 1.0 / std::sqrt((double)n) && c[1] == c[0] * c[0]);
+        std::vector<double> C(2 * (size_t)batch * m, -3.0);
+        CHECK(ace_zgemm_host(0, 0, m, n, batch, A.data(), (long long)m * n, n, 0, Z.data(), (long long)batch * n, n, 0,
+                             C.data(), nullptr, (long long)batch * m, m, 0, 1, nullptr, 0, 0) == ACE_OK);
+        CHECK(finite(C) && C[0] != -3.0);
     }
     // ---- beamformer
     {

@@ -30,8 +30,9 @@ LDS_CU = 160 * 1024
 
 # (ace_lds_request name, source, mangled-name pattern of the kernel(s) it launches, sizes that must fit)
 CASES = [
-    ("i8ah", "ace_i8gemm.hip", [r"i8ah_kernelILb0ELb0E"], [64, 121, 225, 243, 256, 361, 529]),
-    ("i8ah_ky", "ace_i8gemm.hip", [r"i8ah_kernelILb1ELb0E"], [64, 121, 225, 243, 256, 361, 529]),
+    # (300: the largest int8 operand of the operator-level tests, tests/test_gpu_linops.py)
+    ("i8ah", "ace_i8gemm.hip", [r"i8ah_kernelILb0ELb0E"], [64, 121, 225, 243, 256, 300, 361, 529]),
+    ("i8ah_ky", "ace_i8gemm.hip", [r"i8ah_kernelILb1ELb0E"], [64, 121, 225, 243, 256, 300, 361, 529]),
     ("i8ah_fuse", "ace_i8gemm.hip", [r"i8ah_kernelILb0ELb1E"], [64, 121, 225, 256]),
     ("gyk", "ace_i8gemm.hip", [r"10gyk_kernel"], [64, 121, 225, 256]),
     ("gyf", "ace_i8gemm.hip", [r"10gyf_kernel"], [64, 121, 225, 256]),
@@ -87,6 +88,19 @@ def test_static_plus_dynamic_fits_the_cu(static_lds, name, src, pats, sizes):
             dyn = _lib.lds_request(name, m)
             assert static + dyn <= LDS_CU, (
                 f"{kname}: static {static} B + dynamic {dyn} B at m = {m} exceeds the CU's {LDS_CU} B")
+
+
+def test_int8_eligibility_at_the_operator_tests_largest_shape(static_lds):
+    """linops_setup takes the int8 path only when apply_AH and K Y both fit (lds_ok_budget on i8ah_lds_bytes(m)):
+    at m = 300, the largest int8 operand of tests/test_gpu_linops.py, the digit planes of K exceed the 64 KiB
+    default, so both kernels must fit through their derived budgets (160 KiB - static)."""
+    from ace_amd import _lib
+    kernels = static_lds["ace_i8gemm.hip"]
+    for name, pat in (("i8ah", r"i8ah_kernelILb0ELb0E"), ("i8ah_ky", r"i8ah_kernelILb1ELb0E")):
+        (static,) = [v for k, v in kernels.items() if re.search(pat, k)]
+        dyn = _lib.lds_request(name, 300)
+        assert dyn == 128 * (32 * 20 + 16)          # 16 vectors x 8 digits, 20 K-steps of 32 reals + pad
+        assert 64 * 1024 < dyn <= LDS_CU - static   # (past the default limit: the derived budget decides)
 
 
 def test_no_hard_coded_budgets():
