@@ -38,12 +38,19 @@ __device__ int jacobi_eig32(d2* H, d2* Q, int sz, double* wv, JacobiShared& sh) 
     __syncthreads();
     double tr = 0.0;
     for (int k = 0; k < sz; ++k) tr += fabs(H[k * ZHS + k].x);
-    const double abs_tol = 1e-18 * tr;
+    const double hs = eig_prescale(tr);   // 1 unless the rotation tests would overflow or underflow (uniform)
+    const double abs_tol = 1e-18 * (tr * hs);
     const int P = sz >> 1;
     {  // full tile -> packed upper triangle (buffer 0)
         const int j = t & 31, i0 = t >> 5;  // rows i0, i0+8, i0+16, i0+24 of column j
-        const d2 h0 = H[i0 * ZHS + j], h1 = H[(i0 + 8) * ZHS + j];
-        const d2 h2 = H[(i0 + 16) * ZHS + j], h3 = H[(i0 + 24) * ZHS + j];
+        d2 h0 = H[i0 * ZHS + j], h1 = H[(i0 + 8) * ZHS + j];
+        d2 h2 = H[(i0 + 16) * ZHS + j], h3 = H[(i0 + 24) * ZHS + j];
+        if (hs != 1.0) {
+            h0 = cscale(h0, hs);
+            h1 = cscale(h1, hs);
+            h2 = cscale(h2, hs);
+            h3 = cscale(h3, hs);
+        }
         __syncthreads();
         if (i0 <= j) H[up_idx(i0, j)] = h0;
         if (i0 + 8 <= j) H[up_idx(i0 + 8, j)] = h1;
@@ -143,7 +150,10 @@ __device__ int jacobi_eig32(d2* H, d2* Q, int sz, double* wv, JacobiShared& sh) 
         }
     }
     // eigenvalue at position p belongs to eigenvector (Q column) Lab[p]
-    if (t < sz) wv[sh.Lab[cur][t]] = H[cur * ZPACK + up_idx(t, t)].x;
+    if (t < sz) {
+        const double w = H[cur * ZPACK + up_idx(t, t)].x;
+        wv[sh.Lab[cur][t]] = hs != 1.0 ? w / hs : w;
+    }
     __syncthreads();
     return sweeps;
 }

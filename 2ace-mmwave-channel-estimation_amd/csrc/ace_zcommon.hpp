@@ -62,6 +62,20 @@ __device__ __forceinline__ Rot make_rot(double ap, double aq, d2 c, double abs_t
     return r;
 }
 
+// The rotation tests above square entries of H = E E^H: they overflow once tr(H) passes ~1e154 (|E| ~ 1e75) and
+// flush to zero below ~1e-150, and the eigensolver then rotates nothing.  A matrix whose trace lies outside
+// [2^-400, 2^400] is therefore solved as H 2^-e, e = the trace's exponent rounded down to a multiple of 4 (trace in
+// [1, 16)): an exact scaling, under which every rotation, eigenvector and eigenvalue ratio is unchanged.  Any power
+// of two would be exact; a power of 16 also keeps the square roots of scaled entries (frsq of a squared entry, the
+// norms of topk_tri's reflectors) on the mantissas of the unscaled problem, so a trace of 16^j H gives the
+// rotations of H.  e is clamped to +-1020 so that the factor is finite for a subnormal trace (the scaled trace is
+// then merely below 1).  Returns 1 inside the band (no rescaling, the common case).
+__device__ __forceinline__ double eig_prescale(double tr) {
+    if (!(tr > 0x1p+400 || (tr > 0.0 && tr < 0x1p-400)) || !(tr < INFINITY)) return 1.0;
+    const int e = ilogb(tr) & ~3;
+    return scalbn(1.0, -max(-1020, min(1020, e)));
+}
+
 // Packed upper-triangular index of (i, j), i <= j < 32 (528 entries).
 __device__ __forceinline__ int up_idx(int i, int j) { return i * 32 - ((i * (i - 1)) >> 1) + (j - i); }
 

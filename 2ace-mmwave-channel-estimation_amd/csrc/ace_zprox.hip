@@ -326,9 +326,13 @@ __global__ __launch_bounds__(256) void zstep_kernel(ZArgs a) {
         for (int pi = 0; pi < 4; ++pi) maxr = pi < pf.np ? max(maxr, pf.rl[pi]) : maxr;
         const int tkK = min(maxr, tx);
         if (a.tkeig > 0 && (INIT || a.it <= a.tkeig) && maxr <= TK_MAX && tx >= 2) {
+            // (|E| near 1e+-100: topk_tri on H 16^-j like jacobi_eig32, eig_prescale; trace as the certificate sums it)
+            double trh = 0.0;
+            for (int k = 0; k < tx; ++k) trh += fmax(0.0, rs2[k]);
+            const double hs = eig_prescale(trh);
             for (int e = t; e < TXMAX * TXMAX; e += nt) {
                 const int i = e >> 5, c = e & 31;
-                if (i <= c) L1[up_idx(i, c)] = L0[i * HS + c];
+                if (i <= c) L1[up_idx(i, c)] = hs != 1.0 ? cscale(L0[i * HS + c], hs) : L0[i * HS + c];
             }
             __syncthreads();
             __shared__ int tk_s;
@@ -354,6 +358,7 @@ __global__ __launch_bounds__(256) void zstep_kernel(ZArgs a) {
                 double* s2 = wv;
                 double tr = 0.0, top = 0.0;
                 for (int k = 0; k < tx; ++k) tr += fmax(0.0, rs2[k]);
+                tr *= hs;
                 for (int k = 0; k < tkK; ++k) {
                     s2[k] = fmax(0.0, thk[k]);
                     top += s2[k];

@@ -729,6 +729,16 @@ __device__ __forceinline__ void zstep1w_body(const ZArgs& a, int b) {
     double tr = 0.0;
     if (lane < tx) tr = fabs(T0[up_idx(lane, lane)].x);
     tr = wave_sum(tr);
+    // |E| near 1e+-100: the eigensolvers below run on H 16^-j (eig_prescale; they use eigenvalue ratios only)
+    const double hs = eig_prescale(tr);
+    auto scale_h = [&]() {
+        for (int e = lane; e < ZPACK; e += 64) T0[e] = cscale(T0[e], hs);
+        __syncthreads();
+    };
+    if (hs != 1.0) {
+        scale_h();
+        tr *= hs;
+    }
     const double abs_tol = 1e-18 * tr;
     const int P = tx >> 1;
 #ifdef ACE_DEBUG_SWEEPS
@@ -761,6 +771,7 @@ __device__ __forceinline__ void zstep1w_body(const ZArgs& a, int b) {
                 store_f();
             }
             form_h();
+            if (hs != 1.0) scale_h();
         }
     }
     if (!r1 && !tk) {

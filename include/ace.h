@@ -301,6 +301,63 @@ int ace_zgemm_host(int mode, int conj_l, int M, int K, int nb, const double* L, 
                    const double* V, long long nV, int ldv, long long strideV, double* C, const double* E, long long nC,
                    int ldc, long long strideC, int nz, const double* klim, long long nklim, long long klim_stride);
 
+/* ---- test entry: one Z-step (ArgMinZ, the N update and the iteration control) on host arrays --------
+ * The other half of every ADMM iteration on its own (tests/test_gpu_zprox.py compares it with an
+ * extended-precision transcription of inferLowRankV4_multi.m:423-485 and :344-381).  The entry fills a Z-step
+ * argument block and one control block per realisation the way a solve does and calls the solve's Z-step
+ * launcher (init != 0: its init form, mu = 1, N = 0, no iteration control), preceded by the lean steady-state
+ * kernel when lean != 0.  Which kernel runs follows the solver's rule: the one-wave kernel at r = 1, the
+ * four-wave kernel otherwise.
+ *   variant      ACE_VARIANT_A2ONLY | ACE_VARIANT_NUCLEAR
+ *   tx, rx, r    the iterate of a realisation is [r][n], n = tx rx, each column a tx x rx matrix (column-major);
+ *                2 <= tx <= 32 even (the API pads odd tx), 1 <= rx <= 32, 1 <= r <= 32
+ *   m            rows of the thresholds (:364-370) and of rank_profile
+ *   np, rl, fl   the rank profile; np = 0: rank_profile(tx, rx, m, n, 0)
+ *   rank_one     (optional) [batch] per-realisation use_rank_one: profile [1] / [0.95]
+ *   row_mode     scale_by_row (r > 1; r = 1 runs as row mode)
+ *   it           the iteration being controlled (>= 1; init: ignored)
+ *   warm, tkeig, r1lz, zcert   the path switches of the Z-step argument block, passed through
+ *   wmode        r = 1, not init: X holds W = A^H g and the kernel forms X = (Z - N/mu) + W; needs pingpong
+ *   pingpong     Z', N' go to buffers of their own (wmode only), which start from `sentinel`
+ *   lean         the lean kernel first (A2only, r = 1, wmode, warm, n a multiple of 64 else it is a no-op)
+ * Inputs (HOST, c128 as (re, im) doubles): X [batch][r][n]; Z, N [batch][r][n] (NULL: zero; init ignores them);
+ * Q [batch][tx][tx] warm-start eigenvectors (NULL: the buffer starts from `sentinel`; required when warm and not
+ * init); state [batch][ACE_ZP_NIN] doubles and flags [batch][ACE_ZP_NFLAG] int32 (either NULL: zeros, mu = 1),
+ * every control-block field not listed there is zero:
+ *   state: mu, last_res, opt_obj, obj2, nAX2, nY2, nJM2, dY2, dAtY, nAtY, kfcum, kf[0..3]
+ *   flags: done, nzero, kfok, optsrc
+ * The Y-step sums and the dual terms are the caller's numbers (the r = 1 kernel takes them as the fused Y-step
+ * kernel leaves them; the four-wave kernel forms the dual terms itself from Y and K Y buffers, which are zero
+ * here: dAtY = nAtY = 0 there).
+ * Outputs (HOST; each may be NULL): Zo, No [batch][r][n] (in place: the Z, N buffers after the step); Qo
+ * [batch][tx][tx]; optX, Xcur [batch][row_mode ? r : 1][n] (both start from `sentinel`);
+ *   state_out [batch][ACE_ZP_NOUT]: mu, last_res, opt_obj, vbound, kf[0..3], kfcum
+ *   flags_out [batch][ACE_ZP_NFLAGOUT]: iters, done, status, nzero, avok, kfok, optsrc, zit
+ *   tkcnt [2]: top-K tridiagonal uses and fallbacks to the Jacobi eigensolver
+ * ACE_ERR_ARG: bad shapes or missing arrays; ACE_ERR_UNSUPPORTED: a combination no solve makes (wmode without
+ * pingpong or at r > 1 or in the init form, pingpong without wmode, lean outside its conditions, odd tx).  The
+ * producers of the Z-step's inputs that carry solver state (the fused apply_AH, the m-space steady state, the
+ * compact launch and the lazy dual residual) are not reachable from here.
+ * Synchronous; allocates its own device memory. */
+#define ACE_ZP_NIN 15
+#define ACE_ZP_NFLAG 4
+#define ACE_ZP_NOUT 9
+#define ACE_ZP_NFLAGOUT 8
+typedef struct ace_zprox_args {
+    int variant, batch, tx, rx, r, m;
+    int np, rl[4];
+    double fl[4];
+    int init, row_mode, it, fixed_iters;
+    int warm, tkeig, r1lz, zcert, wmode, pingpong, lean, reserved;
+    double tol_rel, tol_abs, rho, sentinel;
+    const unsigned char* rank_one;
+    const double *X, *Z, *N, *Q, *state;
+    const int32_t* flags;
+    double *Zo, *No, *Qo, *optX, *Xcur, *state_out;
+    int32_t *flags_out, *tkcnt;
+} ace_zprox_args;
+int ace_zprox_host(const ace_zprox_args* args);
+
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(
  *                         tx_ant_num, rx_ant_num, cb_amp, cb_angle, rss_final, seed_id)

@@ -123,6 +123,32 @@ void host_only() {
     la.rcols = 2;
     la.path = ACE_LINOP_F64_FUSED;
     CHECK(ace_linop_host(&la) == ACE_ERR_UNSUPPORTED);   // the fused GEMMs run at rcols = 1
+    CHECK(ace_zprox_host(nullptr) == ACE_ERR_ARG);
+    ace_zprox_args za{};
+    za.variant = 7;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_ARG);
+    za.variant = ACE_VARIANT_A2ONLY;
+    za.batch = za.r = za.m = 1;
+    za.tx = za.rx = 33;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_ARG);           // tx, rx <= 32
+    za.tx = za.rx = 4;
+    za.rho = 1.03;
+    za.it = 1;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_ARG);           // NULL X
+    za.X = &d;
+    za.np = 1;
+    za.rl[0] = 5;
+    za.fl[0] = 0.9;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_ARG);           // profile rank beyond tx
+    za.np = 0;
+    za.warm = 1;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_ARG);           // a warm step needs Q
+    za.warm = 0;
+    za.wmode = 1;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_UNSUPPORTED);   // wmode needs ping-pong outputs
+    za.wmode = 0;
+    za.tx = 3;
+    CHECK(ace_zprox_host(&za) == ACE_ERR_UNSUPPORTED);   // odd tx is padded by the API, not here
     CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 3, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
     CHECK(ace_zgemm_host(1, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
     CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 1, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
