@@ -27,6 +27,7 @@ ACE_ST_EIG_NOCONV = 4
 ACE_ST_ROLLBACK = 8
 ACE_ST_RANK_ONE = 128
 ACE_ST_EVAL_DEGENERATE = 256
+ACE_ST_RSS_SKIPPED = 512
 
 ACE_TRAIN_SHARED = 0
 ACE_TRAIN_PER_REALISATION = 1
@@ -133,6 +134,10 @@ def _load():
     lib.ace_evaluate_batch.restype = C.c_int
     lib.ace_evaluate_host.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, up]
     lib.ace_evaluate_host.restype = C.c_int
+    lib.ace_rss_evaluate_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ace_rss_evaluate_batch.restype = C.c_int
+    lib.ace_rss_evaluate_host.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, dp, dp, up]
+    lib.ace_rss_evaluate_host.restype = C.c_int
     lib.ace_spectral_init_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ace_spectral_init_host.restype = C.c_int
     lib.ace_path_counts.argtypes = [C.POINTER(C.c_int64), C.c_int]

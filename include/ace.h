@@ -445,6 +445,34 @@ int ace_evaluate_batch(int batch, int tx, int rx, const double* X, const double*
 int ace_evaluate_host(int batch, int tx, int rx, const double* X, const double* G,
                       double* metrics, uint32_t* status);   /* allocates, copies, synchronous */
 
+/* ---- held-out RSS evaluation (the testbed's accuracy metric) --------------------------------
+ * Evaluate_rss.m (main/src/evaluate_plot_results/ and Numerical_Simulation/src/evaluate_plot_results/),
+ * batched:  rss_eval = abs(cb_test * H),  Evaluation = mean(abs(rss_eval - rss_test) ./ rss_test).
+ * X [batch][n] c128; CB [Pt][n] c128 row-major (row p = test beam p, shared by the batch); rss
+ * [rss_shared ? 1 : batch][Pt] f64 measured AMPLITUDES in X's units (not dBm); all DEVICE.
+ * metrics [batch][4] f64 = {mean_rel, rms_rel, max_rel, n_used}; pred [batch][Pt] f64 = |CB x_b|, may be
+ * NULL; status [batch], may be NULL.  Asynchronous on stream; no allocation, no host synchronisation.
+ *   rel_p    = | |sum_k CB[p][k] X[b][k]| - rss_p | / rss_p     (no conjugate on CB: the product is cb_test * H)
+ *   mean_rel = mean of rel_p over the usable rows (the reference's Evaluation); rms_rel, max_rel their
+ *              root mean square and maximum; n_used the number of usable rows.
+ * n need not be tx*rx (the metric never reshapes).  A realisation's four numbers and its pred row are a
+ * function of (X_b, CB, rss_b, n, Pt) alone: not of batch, of b, or of pred being requested.
+ * batch, n or Pt < 1, a NULL X, CB, rss or metrics and an rss_shared other than 0 or 1 return ACE_ERR_ARG
+ * before any HIP call.
+ * Departures from the reference, which gives Inf or NaN in these cases:
+ *   - a test row whose rss_p is not finite or is <= 0 is left out of the three statistics and of n_used,
+ *     and ACE_ST_RSS_SKIPPED is set; pred is still written for that row;
+ *   - a realisation whose X has a non-finite entry, or that has no usable row (or whose statistics
+ *     overflow), returns 1, 1, 1 and n_used = 0 with ACE_ST_EVAL_DEGENERATE (its pred row is whatever the
+ *     product gives);
+ *   - an all-zero X is not degenerate: pred = 0 and rel_p = 1 on its own. */
+#define ACE_ST_RSS_SKIPPED 512u
+int ace_rss_evaluate_batch(int batch, int n, int Pt, const double* X, const double* CB, const double* rss,
+                           int rss_shared, double* metrics, double* pred, uint32_t* status, void* stream);
+int ace_rss_evaluate_host(int batch, int n, int Pt, const double* X, const double* CB, const double* rss,
+                          int rss_shared, double* metrics, double* pred,
+                          uint32_t* status);   /* allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
