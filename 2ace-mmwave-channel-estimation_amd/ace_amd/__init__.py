@@ -17,6 +17,7 @@ from .beamformer import (svd_beamformer, svd_beamformer_compensation, codebook_b
                          svd_beamformer_host, svd_beamformer_batch, BeamResult)
 from .evaluate import evaluate_host, evaluate_batch, EvalResult  # noqa: F401
 from .rss import evaluate_rss_host, evaluate_rss_batch, dbm_to_amp, RssEval  # noqa: F401
-from . import synth, engine, montecarlo, linops, zprox, realtrace  # noqa: F401
+from .scan import beam_scan_host, beam_scan_batch, ScanResult  # noqa: F401
+from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

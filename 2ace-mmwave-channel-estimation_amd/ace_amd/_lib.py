@@ -138,6 +138,10 @@ def _load():
     lib.ace_rss_evaluate_batch.restype = C.c_int
     lib.ace_rss_evaluate_host.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, dp, dp, up]
     lib.ace_rss_evaluate_host.restype = C.c_int
+    lib.ace_beam_scan_batch.argtypes = [C.c_int] * 5 + [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.ace_beam_scan_batch.restype = C.c_int
+    lib.ace_beam_scan_host.argtypes = [C.c_int] * 5 + [dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, up]
+    lib.ace_beam_scan_host.restype = C.c_int
     lib.ace_spectral_init_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ace_spectral_init_host.restype = C.c_int
     lib.ace_path_counts.argtypes = [C.POINTER(C.c_int64), C.c_int]

@@ -82,3 +82,95 @@ def vs_m(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, firs
     return {"M": np.asarray(Ms, np.int64), "metrics": metrics, "status": status,
             "mean": metrics.mean(axis=1), "n_degenerate": ((status & ACE_ST_EVAL_DEGENERATE) != 0).sum(axis=1),
             "columns": METRICS}
+
+
+BASELINES = ("gain_percsi_ana", "gain_percsi_dig", "aoda_err_est", "gain_est_aoda", "gain_sweep", "aoda_err_sweep")
+
+
+def vs_m_baselines(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, first=0, maxiter=None,
+                   device=None, chunk=CHUNK) -> dict:
+    """``vs_m`` with the yardsticks of Evaluation_Recovery.m beside it: the same loop on the same chunk grid (the
+    four Evaluation_H columns equal ``vs_m``'s bit for bit, and shards compose the same way), plus, per M and
+    realisation ([nM][count] each, keys ``BASELINES``):
+
+      * ``gain_percsi_ana``, ``gain_percsi_dig`` -- ``evaluate_batch(H, H)``: the quantised and the unit-beam
+        gain of the true channel's own singular pair (:195-203, :268-269);
+      * ``aoda_err_est`` -- (|dAoD| + |dAoA|) / 2 of ``angular.estimate_angles`` on the recovered channel against
+        the nearest true path, degrees (:135-146);
+      * ``gain_est_aoda`` -- |w^H H f| on the true H with the 2-bit quantised steering vectors at the estimated
+        angles (:226-229, :271);
+      * ``gain_sweep``, ``aoda_err_sweep`` -- the same two numbers for the pair ``angular.beam_sweep`` picks
+        with Mt = Mr = round(sqrt(M)) beams (about the same number of probes) at ``snr_db`` (:232-259, :273).
+
+    The gains are in ``gain_ana``'s unit, so that the columns divide into each other: the true H as InferADMM
+    sees it (divided by ||B||) and quantised beams with Quantize_PS's own 1 / sqrt(antennas) each, which is what
+    ``evaluate_batch`` applies to ``gain_ana`` (the scan runs on the unit-modulus beams, exact powers of j, and
+    the modulus is divided by sqrt(tx rx)).  The sweep itself, whose noise is
+    absolute, runs on the channel at the synth's own scale (``synth.channel``).  The realisation's recovery runs
+    once; each gain is read off one beam scan of the true H; only per-realisation metrics leave the device.  A
+    realisation whose estimate is degenerate (a non-finite recovery) gets ``gain_est_aoda`` 0 and ``aoda_err_est``
+    = the width of the angular range, so that means stay finite.  Square arrays only, for the reason ``vs_m`` gives."""
+    import torch
+    from . import angular, synth
+    from .engine import randperm
+    from .pipeline import infer_low_rank_pipeline_batch
+    from .scan import beam_scan_batch
+    from .solver import VARIANTS, synth_problem
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if tx != rx:
+        raise ValueError(f"vs_m_baselines needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    count, first, chunk = int(count), int(first), int(chunk)
+    if count < 1 or first < 0 or chunk < 1:
+        raise ValueError("count and chunk must be >= 1 and first >= 0")
+    Ms = [int(M) for M in M_list]
+    dev = torch.device("cuda" if device is None else device)
+    cfg = pipeline_cfg(VARIANTS[method])
+    R = cfg.restarts
+    kw = {} if maxiter is None else {"maxiter": int(maxiter)}
+    metrics = np.empty((len(Ms), count, 4), np.float64)
+    status = np.empty((len(Ms), count), np.uint32)
+    base = {k: np.empty((len(Ms), count), np.float64) for k in BASELINES}
+    end = first + count
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    Wq, Fq = up(angular.quantize_ps(angular.dictionary(rx)[0])), up(angular.quantize_ps(angular.dictionary(tx)[0]))
+
+    def gain_at(H, W, F, p, q):
+        """|w^H H f| / sqrt(tx rx) from the scan's power of the true H at pair (p, q) per realisation; 0 where p < 0."""
+        pw = beam_scan_batch(H, W, F, 1, want_power=True).power
+        ok = p >= 0
+        g = pw[torch.arange(pw.shape[0], device=dev), p.long().clamp(min=0), q.long().clamp(min=0)].sqrt() / math.sqrt(tx * rx)
+        return torch.where(ok, g, torch.zeros_like(g)), ok
+
+    for k, M in enumerate(Ms):
+        mt = math.floor(M * cfg.cc_frac)
+        nb = max(1, int(round(math.sqrt(M))))
+        Ws, Fs = up(angular.sweep_beams(rx, nb)[0]), up(angular.sweep_beams(tx, nb)[0])
+        for c0 in range(first // chunk * chunk, end, chunk):
+            A, B, _, H = synth_problem(seed, c0, chunk, M, tx, rx, L=L, snr_db=snr_db, device=dev)
+            tr = np.stack([np.stack([randperm(seed, (c0 + b) * R + i, M, mt) for i in range(R)])
+                           for b in range(chunk)])
+            rec = infer_low_rank_pipeline_batch(A, B, tx, rx, tr, variant=method, restarts=R, **kw)
+            ev = evaluate_batch(rec.X, H, tx, rx)
+            pc = evaluate_batch(H, H, tx, rx)
+            aod_e, aoa_e, _, pe, qe = angular.estimate_angles(rec.X, tx, rx)
+            g_est, ok = gain_at(H, Wq, Fq, pe, qe)
+            Hraw = up(np.stack([synth.channel(seed, c0 + b, tx, rx, L) for b in range(chunk)]))
+            aod_s, aoa_s, ps, qs = angular.beam_sweep(Hraw, tx, rx, nb, nb, snr_db=snr_db, seed=seed, first=c0)
+            g_sw, _ = gain_at(H, Ws, Fs, ps, qs)
+            tru = [synth.paths(seed, c0 + b, L) for b in range(chunk)]
+            aod_t, aoa_t = np.stack([t[0] for t in tru]), np.stack([t[1] for t in tru])
+            err_e = angular.aoda_err(aod_e.cpu().numpy(), aoa_e.cpu().numpy(), aod_t, aoa_t)
+            err_e[~ok.cpu().numpy()] = angular.SEARCH_DEG
+            cols = {"gain_percsi_ana": pc.gain_ana.cpu().numpy(), "gain_percsi_dig": pc.gain_dig.cpu().numpy(),
+                    "aoda_err_est": err_e, "gain_est_aoda": g_est.cpu().numpy(), "gain_sweep": g_sw.cpu().numpy(),
+                    "aoda_err_sweep": angular.aoda_err(aod_s.cpu().numpy(), aoa_s.cpu().numpy(), aod_t, aoa_t)}
+            lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+            rows = slice(lo - first, hi - first)
+            metrics[k, rows] = ev.metrics[lo - c0:hi - c0].cpu().numpy()
+            status[k, rows] = ev.status[lo - c0:hi - c0].cpu().numpy().view(np.uint32)
+            for name, v in cols.items():
+                base[name][k, rows] = v[lo - c0:hi - c0]
+    return {"M": np.asarray(Ms, np.int64), "metrics": metrics, "status": status,
+            "mean": metrics.mean(axis=1), "n_degenerate": ((status & ACE_ST_EVAL_DEGENERATE) != 0).sum(axis=1),
+            "columns": METRICS, **base, "baseline_mean": {name: v.mean(axis=1) for name, v in base.items()}}

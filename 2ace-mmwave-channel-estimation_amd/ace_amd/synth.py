@@ -82,6 +82,15 @@ def channel(seed, real, tx, rx, L=3):
     return np.sum(g[None, :] * (np.cos(ph) + 1j * np.sin(ph)), axis=1)
 
 
+def paths(seed, real, L=3):
+    """(aod_deg [L], aoa_deg [L], gains [L]) of realisation ``real``: the numbers ``channel`` draws, so that
+    sum_l gains[l] exp(1j kappa (sin(aod_l) t - sin(aoa_l) r)) over k = r + rx t is ``channel`` bit for bit."""
+    st = stream_id(ST_ANGLES, real)
+    u = u01(seed, st, np.arange(2 * L, dtype=np.uint64))
+    g = normal_pairs(seed, stream_id(ST_GAINS, real), L) * np.sqrt(0.5)
+    return (u[:L] - 0.5) * 95.0, (u[L:] - 0.5) * 95.0, g / np.sqrt(np.sum(np.abs(g) ** 2))
+
+
 def measurements(seed, real, A, vecH, snr_db=30.0):
     m = A.shape[0]
     sigma2 = 10.0 ** (-snr_db / 10.0)

@@ -473,6 +473,32 @@ int ace_rss_evaluate_host(int batch, int n, int Pt, const double* X, const doubl
                           int rss_shared, double* metrics, double* pred,
                           uint32_t* status);   /* allocates, copies, synchronous */
 
+/* ---- beam scan (exhaustive sweep and angular map) ----------------------------------------------
+ * MyBeamSweeping.m:93-125 (RSS = |kron(transpose(F), W') vec(H) + noise|^2 and its argmax) and the angular
+ * map Leakage = A_Rx' * H * A_Tx of Sparse_Channel_Formulation.m:149, batched and fused with the selection.
+ * X [batch][d0*d1] c128 with mat(x)(i, j) = x[i + d0*j] (the layout ace_evaluate_batch takes); W0 [Q0][d0]
+ * c128 row-major, beams on the leading index, applied conjugated; F1 [Q1][d1] c128 row-major, beams on the
+ * trailing index, applied plain; noise NULL or [batch][Q1*Q0] c128; all DEVICE.
+ *   y[b][p][q] = sum_i sum_j conj(W0[q][i]) x_b[i + d0*j] F1[p][j]      (w' * H * f)
+ *   P          = |y + noise|^2,   flat index f = p*Q0 + q                (:124-125 zero-based: p = ind_F - 1, q = ind_W - 1)
+ * top_pow, top_idx [batch][K]: the K largest P of the realisation in descending order, equal powers by
+ * increasing f; total [batch] (may be NULL): the sum of P; power [batch][Q1*Q0] (may be NULL): the whole
+ * map; status [batch] (may be NULL).  Asynchronous on stream; no allocation, no host synchronisation, no
+ * workspace.  A realisation's outputs are a function of (x_b, W0, F1, noise_b, the sizes, K) alone: not of
+ * batch, of b, of power or total being requested, or of the stream.
+ * 1 <= d0, d1 <= 32, 1 <= Q0, Q1 <= 4096, 1 <= K <= min(16, Q0*Q1), batch >= 1; bad sizes and a NULL X, W0,
+ * F1, top_pow or top_idx return ACE_ERR_ARG before any HIP call.  ACE_ERR_UNSUPPORTED when the kernel's
+ * dynamic LDS request is refused.
+ * A realisation whose x, or whose noise row, holds a non-finite value returns powers 0, indices -1, total 0
+ * and ACE_ST_EVAL_DEGENERATE (its power row is whatever the product gives); an all-zero x is not degenerate.
+ * A non-finite beam entry is the caller's error and is not checked. */
+int ace_beam_scan_batch(int batch, int d0, int d1, int Q0, int Q1, const double* X, const double* W0,
+                        const double* F1, const double* noise, int K, double* top_pow, int32_t* top_idx,
+                        double* total, double* power, uint32_t* status, void* stream);
+int ace_beam_scan_host(int batch, int d0, int d1, int Q0, int Q1, const double* X, const double* W0,
+                       const double* F1, const double* noise, int K, double* top_pow, int32_t* top_idx,
+                       double* total, double* power, uint32_t* status);   /* allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
@@ -542,7 +568,7 @@ int ace_path_counts(int64_t* counts, int reset);
 
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
- * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order).  With the kernel's static LDS
+ * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
 int ace_lds_request(const char* kernel, int m, size_t* bytes);
