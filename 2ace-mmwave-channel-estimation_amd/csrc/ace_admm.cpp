@@ -89,8 +89,6 @@ void linops_carve(Carver& cv, bool shared, int batch, int m, int n, LinOps* L) {
 //                       (topk_tri) in the init Z-step and iterations <= it; later ones run the warm Jacobi
 //                       (default 6; 0: Jacobi throughout); ACE_TK_TRACE=1: its use and fallback counts
 //                       on stderr at the end of the solve
-//   ACE_I8_COMPACT=1    the fused apply_AH compacts a block's realisations outside the m-space form onto the
-//                       first MFMA row tiles (pending its GPU validation: off)
 //   ACE_ZCERT=0         the four-wave Z-step (r-column stages) always runs its eigensolver (no Ky Fan
 //                       certificate)
 struct Knobs {

@@ -13,6 +13,7 @@
 // branch-free with one barrier.  Stop: a pre-sweep test over all off-diagonals
 // (|h_pq| <= 1e-18 tr H or |h_pq|^2 <= 1e-32 |h_pp h_qq|), so no confirming sweep runs.
 #pragma once
+#include "ace_mfma.hpp"
 #include "ace_zcommon.hpp"
 
 namespace ace {
@@ -172,10 +173,7 @@ __device__ __forceinline__ void mm32_acc(const d2* A, const d2* B, d4v& cr, d4v&
         d2 bv = CTB ? B[(j0 + (lane & 15)) * ZHS + kk] : B[kk * ZHS + j0 + (lane & 15)];
         if (CTA) av.y = -av.y;
         if (CTB) bv.y = -bv.y;
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, bv.x, cr, 0, 0, 0);
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-av.y, bv.y, cr, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, bv.y, ci, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, bv.x, ci, 0, 0, 0);
+        cmma(cr, ci, av, bv);
     }
 }
 template <bool CTA, bool CTB>

@@ -11,9 +11,7 @@
 //   D^T[j][i'] = sum_k' Vhat[j][k'] * Lhat[i'][k']     (j: realisation, i' = 2i + c)
 //   Lhat[2i+c][2k+d] = c==d ? Re L_ik : (c==0 ? -Im L_ik : Im L_ik)
 //
-// MFMA operand maps (verified on MI355X with asymmetric data, tools/probe_fp64.hip):
-//   A-frag lane l: A[row = l&15][k = l>>4];  B-frag: B[k = l>>4][col = l&15];
-//   D lane l, reg r: D[row = (l>>4) + 4r][col = l&15].
+// MFMA operand and result lane maps: ace_mfma.hpp.
 // Here A = Vhat (rows = realisations), B = Lhat^T (cols = output reals), so each
 // output row (one realisation) is written as 16 consecutive doubles = 128 B.
 //
@@ -24,6 +22,7 @@
 // to the same XCD (blocks b and b+8 share an XCD under round-robin dispatch) so
 // the panel is served from that XCD's L2.
 #include "ace_common.hpp"
+#include "ace_mfma.hpp"
 
 namespace ace {
 
@@ -156,7 +155,7 @@ __global__ __launch_bounds__(CF::NT) void zgemm_kernel(int M, int K, int nb, con
             for (int jj = 0; jj < TJ; ++jj)
 #pragma unroll
                 for (int ii = 0; ii < TI; ++ii)
-                    acc[jj][ii] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[jj], bf[ii], acc[jj][ii], 0, 0, 0);
+                    acc[jj][ii] = mfma64(af[jj], bf[ii], acc[jj][ii]);
         }
         if (ks + 1 < ksteps) lstore(buf ^ 1);
         __syncthreads();
@@ -331,11 +330,8 @@ __global__ __launch_bounds__(CF::NT) void zgemm3m_kernel(int M, int K, int nb, c
 #pragma unroll
             for (int jj = 0; jj < TJ; ++jj)
 #pragma unroll
-                for (int cc = 0; cc < TC; ++cc) {
-                    p1[jj][cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[jj], br[cc], p1[jj][cc], 0, 0, 0);
-                    p2[jj][cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[jj], bi[cc], p2[jj][cc], 0, 0, 0);
-                    p3[jj][cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[jj], bs[cc], p3[jj][cc], 0, 0, 0);
-                }
+                for (int cc = 0; cc < TC; ++cc)
+                    mma3m(p1[jj][cc], p2[jj][cc], p3[jj][cc], ar[jj], ai[jj], as[jj], br[cc], bi[cc], bs[cc]);
         }
         if (ks + 1 < ksteps) lstore(buf ^ 1);
         __syncthreads();
@@ -352,8 +348,7 @@ __global__ __launch_bounds__(CF::NT) void zgemm3m_kernel(int M, int K, int nb, c
                 const int jl = wj * (BJ / CF::WJ) + jj * 16 + (lane >> 4) + 4 * r;
                 const int j = j0 + jl;
                 const int i = i0 + wi * (BC / CF::WI) + (lane & 15);
-                const double a = p1[jj][0][r], b = p2[jj][0][r];
-                const d2 gv = make_double2(a - b, p3[jj][0][r] - a - b);
+                const d2 gv = comb3m(p1[jj][0][r], p2[jj][0][r], p3[jj][0][r]);
                 double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
                 if (j < nb && i < M) {
                     const long long off = (long long)j * ldc + i;
@@ -418,8 +413,7 @@ __global__ __launch_bounds__(CF::NT) void zgemm3m_kernel(int M, int K, int nb, c
                         if (rs[j].done) continue;
                     }
                     const long long off = 2LL * ((long long)j * ldc + i);
-                    const double a = p1[jj][cc][r], b = p2[jj][cc][r];
-                    d2 v = make_double2(a - b, p3[jj][cc][r] - a - b);
+                    d2 v = comb3m(p1[jj][cc][r], p2[jj][cc][r], p3[jj][cc][r]);
                     if (MODE != 0) {
                         d2 e = *reinterpret_cast<const d2*>(E + off);
                         if constexpr (FE) e = csub(e, cscale(*reinterpret_cast<const d2*>(E2 + off), 1.0 / rs[j].mu));

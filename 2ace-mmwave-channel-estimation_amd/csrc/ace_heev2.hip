@@ -30,6 +30,7 @@
 
 #include "ace_common.hpp"
 #include "ace_host.hpp"
+#include "ace_mfma.hpp"
 #include "ace_pipe.hpp"
 
 namespace ace {
@@ -115,8 +116,7 @@ __device__ __forceinline__ Refl zlarfg_dev(d2 alpha, double xn2) {
     return r;
 }
 
-// complex 16 x 16 accumulator in the f64 MFMA D layout: lane l, register j holds D[(l >> 4) + 4 j][l & 15];
-// operands of k-step s: A lane l = A[l & 15][4 s + (l >> 4)], B lane l = B[4 s + (l >> 4)][l & 15]
+// complex 16 x 16 accumulator in the f64 MFMA D layout (ace_mfma.hpp); k-step s takes k = 4 s + (l >> 4)
 struct Cacc {
     d4v r, i;
 };
@@ -126,15 +126,7 @@ __device__ __forceinline__ Cacc cacc0() {
     a.i = d4v{0.0, 0.0, 0.0, 0.0};
     return a;
 }
-__device__ __forceinline__ d4v mfma64(double a, double b, d4v c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void cmma(Cacc& d, d2 a, d2 b) {   // d += a b, one k-step
-    d.r = mfma64(a.x, b.x, d.r);
-    d.r = mfma64(-a.y, b.y, d.r);
-    d.i = mfma64(a.x, b.y, d.i);
-    d.i = mfma64(a.y, b.x, d.i);
-}
+__device__ __forceinline__ void cmma(Cacc& d, d2 a, d2 b) { ace::cmma(d.r, d.i, a, b); }   // d += a b, one k-step
 __device__ __forceinline__ d2 cget(const Cacc& a, int j) { return make_double2(a.r[j], a.i[j]); }
 
 __device__ __forceinline__ double row_shr1(double x) {   // lane l <- lane l - 1 within each 16-lane row (lane 0: 0)

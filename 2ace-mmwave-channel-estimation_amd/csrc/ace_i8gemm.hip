@@ -34,6 +34,7 @@
 // realisation's m entries in a pre-pass.  A non-finite bound yields NaN outputs for that
 // realisation (the f64 product would not be finite either).
 #include "ace_i8.hpp"
+#include "ace_mfma.hpp"
 #include "ace_zcommon.hpp"
 
 namespace ace {
@@ -678,9 +679,6 @@ __global__ __launch_bounds__(256) void i8_expand_kernel(int m, int n, const doub
 constexpr int GSK = ACE_GSK;          // f64 K-steps (4 complex each) per pipeline stage
 constexpr int GRB = 16;         // realisations per work-group (one f64 MFMA row tile)
 __host__ __device__ __forceinline__ int gyk_mp(int m) { return (m + 31) & ~31; }
-struct GSet {
-    d2 f[GSK][2];
-};
 
 // One output of the fused Y-step (ArgMinY with its zero guard, inferLowRankV4_multi.m:511-533, and
 // the M update): g from the 3M accumulators, AX = (Y - M/mu) - g, Y', M', and the five sums plus the
@@ -691,8 +689,8 @@ __device__ __forceinline__ void ystep_elem(double e1, double e2, double e3, doub
                                            d2& gv, d2& ax, d2& mn, d2& y, double (&v)[9]) {
 #pragma clang fp contract(off)
     // (written out in scalars: the pragma governs only the operations spelled here, not those of
-    // the complex helpers)
-    gv = make_double2(e1 - e2, e3 - e1 - e2);
+    // the complex helpers; comb3m only subtracts, so it has nothing to contract)
+    gv = comb3m(e1, e2, e3);
     const double imu = 1.0 / mu;
     const double pr = mii.x * imu, pi = mii.y * imu;   // M / mu
     ax = make_double2((yo.x - pr) - gv.x, (yo.y - pi) - gv.y);
@@ -969,67 +967,11 @@ __device__ __forceinline__ void gyk_body(int nb, int m, const GykArgs& a, unsign
     STAMP(1);
 
     // ---- g = G T: wave w owns output tiles 2w, 2w + 1 (16 complex each)
-    const int nct = mp / 16, nks = mp / 4, nstage = nks / GSK;
-    const int ct0 = min(2 * w, nct - 1), ct1 = min(2 * w + 1, nct - 1);
-    const d2* gp0 = reinterpret_cast<const d2*>(a.Gf) + (long long)ct0 * 64 + lane;
-    const d2* gp1 = reinterpret_cast<const d2*>(a.Gf) + (long long)ct1 * 64 + lane;
-    auto gload = [&](GSet& gs, int s) {
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) {
-            const long long ks = min(GSK * s + kk, nks - 1);
-#ifdef ACE_GYK_PROBE_NO_G
-            gs.f[kk][0] = make_double2(1.0 + ks, 0.5);
-            gs.f[kk][1] = make_double2(0.5, 1.0 + ks);
-#else
-            gs.f[kk][0] = gp0[ks * nct * 64];
-            gs.f[kk][1] = gp1[ks * nct * 64];
-#endif
-        }
-    };
+    const int nct = mp / 16, nks = mp / 4;
+    const d2* const gp[2] = {reinterpret_cast<const d2*>(a.Gf) + (long long)min(2 * w, nct - 1) * 64 + lane,
+                             reinterpret_cast<const d2*>(a.Gf) + (long long)min(2 * w + 1, nct - 1) * 64 + lane};
     d4v p1[2], p2[2], p3[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) p1[c] = p2[c] = p3[c] = d4v{0.0, 0.0, 0.0, 0.0};
-    const d2* trow = Ts + (lane & 15) * tst + (lane >> 4);
-    struct TSet {
-        d2 v[GSK];
-    };
-    auto tload = [&](TSet& ts, int s) {   // T fragments of a stage, one stage ahead of their use
-        const int s2 = min(s, nstage - 1);
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) ts.v[kk] = trow[4 * (GSK * s2 + kk)];
-    };
-    auto gcomp = [&](const GSet& gs, const TSet& ts) {
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) {
-            const d2 v = ts.v[kk];
-            const double ar = v.x, ai = v.y, as = v.x + v.y;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const d2 l = gs.f[kk][c];
-                p1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, l.x, p1[c], 0, 0, 0);
-                p2[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, l.y, p2[c], 0, 0, 0);
-                p3[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, l.x + l.y, p3[c], 0, 0, 0);
-            }
-        }
-    };
-    {
-        GSet gA, gB;
-        TSet tA, tB;
-        gload(gA, 0);
-        tload(tA, 0);
-        for (int s = 0; s < nstage; s += 2) {   // nstage is even (mp multiple of 32)
-            gload(gB, s + 1);
-            tload(tB, s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            gcomp(gA, tA);
-            __builtin_amdgcn_sched_barrier(0);
-            gload(gA, s + 2);
-            tload(tA, s + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            gcomp(gB, tB);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    frag_mv<2, GSK>(gp, Ts, tst, nct, nks, lane, p1, p2, p3);
     // the Y-step inputs of the lane's 8 elements as one batch of loads (unconditional, clamped
     // addresses; per-element branches would serialise 8 memory round trips).  Issued after the
     // G T loop: held across it they would push the kernel past 256 VGPRs into scratch.
@@ -1368,7 +1310,7 @@ template <int TPW>
 __global__ __launch_bounds__(64 * 16 / TPW, 1) void msr_kernel(MsrArgs a, ZArgs za) {
     constexpr int NTW = 64 * 16 / TPW;   // threads
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int mp = 256, tst = mp + 1, nct = mp / 16, nks = mp / 4, nstage = nks / MGSK;
+    constexpr int mp = 256, tst = mp + 1, nct = mp / 16, nks = mp / 4;
     d2* Ts = reinterpret_cast<d2*>(smem);        // [16][tst]: T
     d2* Ss = Ts + GRB * tst;                     // [4 TPW][NTW]: S of the thread's outputs (thread-private)
     __shared__ double red[8][GRB][9];
@@ -1454,8 +1396,9 @@ __global__ __launch_bounds__(64 * 16 / TPW, 1) void msr_kernel(MsrArgs a, ZArgs 
     }
     __syncthreads();   // (every thread is done with the flush flags)
     if (t < GRB) flg_s[t] = 0;
-    const d2* gp = reinterpret_cast<const d2*>(a.Gf) + (long long)(TPW * w) * 64 + lane;   // tile TPW w + c: + 64 c
-    const d2* trow = Ts + (lane & 15) * tst + (lane >> 4);
+    const d2* gp[TPW];   // the lane's entry of G's tile TPW w + c
+#pragma unroll
+    for (int c = 0; c < TPW; ++c) gp[c] = reinterpret_cast<const d2*>(a.Gf) + (long long)(TPW * w + c) * 64 + lane;
     int cnt = 0;   // m-space steps of realisation t (ace_prof_msp_steps)
     bool mylive = t < GRB && live_s[t] && !(flg_s[t] & 4);
     // best iterates, deferred like gyf_kernel's opt_Y / opt_S: the previous iterate's Y (in yv) and S
@@ -1486,61 +1429,9 @@ __global__ __launch_bounds__(64 * 16 / TPW, 1) void msr_kernel(MsrArgs a, ZArgs 
         }
         __syncthreads();
         MSR_STAMP(0);
-        // g = G T: gyk_body's 3M product, the same k order
+        // g = G T: gyk_body's frag_mv, so the same 3M products in the same k order
         d4v p1[TPW], p2[TPW], p3[TPW];
-#pragma unroll
-        for (int c = 0; c < TPW; ++c) p1[c] = p2[c] = p3[c] = d4v{0.0, 0.0, 0.0, 0.0};
-        {
-            struct GS {
-                d2 f[MGSK][TPW];
-            };
-            struct TS {
-                d2 v[MGSK];
-            };
-            auto gload = [&](GS& gs, int s) {
-#pragma unroll
-                for (int kk = 0; kk < MGSK; ++kk) {
-                    const long long ks = min(MGSK * s + kk, nks - 1);
-#pragma unroll
-                    for (int c = 0; c < TPW; ++c) gs.f[kk][c] = gp[ks * nct * 64 + 64 * c];
-                }
-            };
-            auto tload = [&](TS& ts, int s) {
-                const int s2 = min(s, nstage - 1);
-#pragma unroll
-                for (int kk = 0; kk < MGSK; ++kk) ts.v[kk] = trow[4 * (MGSK * s2 + kk)];
-            };
-            auto gcomp = [&](const GS& gs, const TS& ts) {
-#pragma unroll
-                for (int kk = 0; kk < MGSK; ++kk) {
-                    const d2 v = ts.v[kk];
-                    const double ar = v.x, ai = v.y, as = v.x + v.y;
-#pragma unroll
-                    for (int c = 0; c < TPW; ++c) {
-                        const d2 l = gs.f[kk][c];
-                        p1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, l.x, p1[c], 0, 0, 0);
-                        p2[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, l.y, p2[c], 0, 0, 0);
-                        p3[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, l.x + l.y, p3[c], 0, 0, 0);
-                    }
-                }
-            };
-            GS gA, gB;
-            TS tA, tB;
-            gload(gA, 0);
-            tload(tA, 0);
-            for (int s = 0; s < nstage; s += 2) {
-                gload(gB, s + 1);
-                tload(tB, s + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                gcomp(gA, tA);
-                __builtin_amdgcn_sched_barrier(0);
-                gload(gA, s + 2);
-                tload(tA, s + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                gcomp(gB, tB);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        frag_mv<TPW, MGSK>(gp, Ts, tst, nct, nks, lane, p1, p2, p3);
         MSR_STAMP(1);
         __syncthreads();   // every wave has read T: the Y-step writes AX into its slots
         MSR_STAMP(2);

@@ -30,6 +30,7 @@
 // products are formed in another order (the nuclear refinement is rounding-chaotic beyond ~60
 // iterations: DESIGN §6).
 #include "ace_common.hpp"
+#include "ace_mfma.hpp"
 #include "ace_zcommon.hpp"
 
 namespace ace {
@@ -40,71 +41,18 @@ constexpr int GRB = 16;    // realisations per work-group (one f64 MFMA row tile
 constexpr int GSK = 4;     // f64 K-steps (4 complex each) per pipeline stage
 __host__ __device__ __forceinline__ int nms_mp(int m) { return (m + 31) & ~31; }
 
-struct GSet {
-    d2 f[GSK][2];
-};
-struct TSet {
-    d2 v[GSK];
-};
-
 // P[c][r] (3M accumulators) of the lane's 2 x 4 outputs of  out_i = sum_k L[i][k] v_k  for the
-// 16 realisation rows held in LDS (Ts, row stride tst), L in fragment order (launch_gyk_gfrag).
-__device__ __forceinline__ void frag_mv(const d2* __restrict__ Lf, const d2* Ts, int tst, int mp, int lane, int w,
+// 16 realisation rows held in LDS (Ts, row stride tst), L in fragment order (launch_gyk_gfrag):
+// frag_mv on this wave's tiles 2w, 2w + 1, as gyk_body (ace_i8gemm.hip)
+__device__ __forceinline__ void wave_mv(const double* Lf, const d2* Ts, int tst, int mp, int lane, int w,
                                         d4v (&p1)[2], d4v (&p2)[2], d4v (&p3)[2]) {
-    const int nct = mp / 16, nks = mp / 4, nstage = nks / GSK;
-    const int ct0 = min(2 * w, nct - 1), ct1 = min(2 * w + 1, nct - 1);
-    const d2* gp0 = Lf + (long long)ct0 * 64 + lane;
-    const d2* gp1 = Lf + (long long)ct1 * 64 + lane;
-    auto gload = [&](GSet& gs, int s) {
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) {
-            const long long ks = min(GSK * s + kk, nks - 1);
-            gs.f[kk][0] = gp0[ks * nct * 64];
-            gs.f[kk][1] = gp1[ks * nct * 64];
-        }
-    };
-    const d2* trow = Ts + (lane & 15) * tst + (lane >> 4);
-    auto tload = [&](TSet& ts, int s) {
-        const int s2 = min(s, nstage - 1);
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) ts.v[kk] = trow[4 * (GSK * s2 + kk)];
-    };
-    auto gcomp = [&](const GSet& gs, const TSet& ts) {
-#pragma unroll
-        for (int kk = 0; kk < GSK; ++kk) {
-            const d2 v = ts.v[kk];
-            const double ar = v.x, ai = v.y, as = v.x + v.y;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const d2 l = gs.f[kk][c];
-                p1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, l.x, p1[c], 0, 0, 0);
-                p2[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, l.y, p2[c], 0, 0, 0);
-                p3[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, l.x + l.y, p3[c], 0, 0, 0);
-            }
-        }
-    };
-#pragma unroll
-    for (int c = 0; c < 2; ++c) p1[c] = p2[c] = p3[c] = d4v{0.0, 0.0, 0.0, 0.0};
-    GSet gA, gB;
-    TSet tA, tB;
-    gload(gA, 0);
-    tload(tA, 0);
-    for (int s = 0; s < nstage; s += 2) {   // nstage is even (mp a multiple of 32)
-        gload(gB, s + 1);
-        tload(tB, s + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        gcomp(gA, tA);
-        __builtin_amdgcn_sched_barrier(0);
-        gload(gA, s + 2);
-        tload(tA, s + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        gcomp(gB, tB);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    const int nct = mp / 16;
+    const d2* L = reinterpret_cast<const d2*>(Lf) + lane;
+    const d2* const gp[2] = {L + (long long)min(2 * w, nct - 1) * 64, L + (long long)min(2 * w + 1, nct - 1) * 64};
+    frag_mv<2, GSK>(gp, Ts, tst, nct, mp / 4, lane, p1, p2, p3);
 }
 __device__ __forceinline__ d2 frag_out(const d4v (&p1)[2], const d4v (&p2)[2], const d4v (&p3)[2], int c, int r) {
-    const double e1 = p1[c][r], e2 = p2[c][r];
-    return make_double2(e1 - e2, p3[c][r] - e1 - e2);
+    return comb3m(p1[c][r], p2[c][r], p3[c][r]);
 }
 __device__ __forceinline__ double cdotr(d2 a, d2 b) { return a.x * b.x + a.y * b.y; }   // Re(conj(a) b)
 
@@ -147,7 +95,7 @@ __global__ __launch_bounds__(NT, 1) void nms_kernel(int nb, int m, NmsArgs a, ZA
             }
             __syncthreads();
             d4v p1[2], p2[2], p3[2];
-            frag_mv(reinterpret_cast<const d2*>(a.Kf), Ts, tst, mp, lane, w, p1, p2, p3);
+            wave_mv(a.Kf, Ts, tst, mp, lane, w, p1, p2, p3);
             double q[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int c = 0; c < 2; ++c)
@@ -205,7 +153,7 @@ __global__ __launch_bounds__(NT, 1) void nms_kernel(int nb, int m, NmsArgs a, ZA
     __syncthreads();
     // ---- g = G T
     d4v p1[2], p2[2], p3[2];
-    frag_mv(reinterpret_cast<const d2*>(a.Gf), Ts, tst, mp, lane, w, p1, p2, p3);
+    wave_mv(a.Gf, Ts, tst, mp, lane, w, p1, p2, p3);
 
     // ---- pass 1: the Y-step, E_new = a_z E_prev + A^H g as (e_new, K e_new), and the sums
     double v[4][NSUM];

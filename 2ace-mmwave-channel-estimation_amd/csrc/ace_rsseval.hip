@@ -9,9 +9,8 @@
 // the usable rows, with their count.
 //
 // One fused kernel.  The product CB X^T runs on the f64 matrix cores (v_mfma_f64_16x16x4_f64) in the 3M
-// form of ace_gemm.hip (P1 = Xr Cr, P2 = Xi Ci, P3 = (Xr + Xi)(Cr + Ci); Re = P1 - P2, Im = P3 - P1 - P2),
-// with the MFMA operand maps verified there: A = X (rows: realisations), B = CB^T (columns: test rows),
-// D lane l, reg r -> realisation (l >> 4) + 4 r, test row l & 15.
+// form (mma3m / comb3m and the lane maps of ace_mfma.hpp): A = X (rows: realisations), B = CB^T (columns:
+// test rows), so D lane l, reg r is realisation (l >> 4) + 4 r, test row l & 15.
 //
 // Tiling.  A work-group owns RS_BJ = 16 realisations and walks ALL the test rows in tiles of RS_BC = 128
 // (8 waves side by side along the test rows, one 16 x 16 block of three accumulators each), RS_BK = 16
@@ -43,6 +42,7 @@
 // 1, 1, 1, n_used = 0 and ACE_ST_EVAL_DEGENERATE.  An all-zero X is not degenerate: pred = 0, rel = 1.
 #include "ace_common.hpp"
 #include "ace_host.hpp"
+#include "ace_mfma.hpp"
 
 #pragma clang fp contract(off)
 
@@ -161,20 +161,15 @@ __global__ __launch_bounds__(RS_NT) void rsseval_kernel(int batch, int n, int Pt
                 if (s + 1 < steps) fread(s + 1, (i + 1) & 1);
                 if (s + RS_RING < steps) gload(s + RS_RING, i);
 #pragma unroll
-                for (int kk = 0; kk < RS_BK / 4; ++kk) {
-                    const d2 v = fv[i & 1][kk], l = fl[i & 1][kk];
-                    p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, l.x, p1, 0, 0, 0);
-                    p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, l.y, p2, 0, 0, 0);
-                    p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x + v.y, l.x + l.y, p3, 0, 0, 0);
-                }
+                for (int kk = 0; kk < RS_BK / 4; ++kk) mma3m(p1, p2, p3, fv[i & 1][kk], fl[i & 1][kk]);
                 if (++ks == ksteps) {   // end of a tile: modulus, relative error, running statistics
                     const int p = tile * RS_BC + col;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int j = j0 + (lane >> 4) + 4 * r;
                         if (p < Pt && j < batch) {
-                            const double a = p1[r], b = p2[r];
-                            const double pr = hypot(a - b, p3[r] - a - b);
+                            const d2 g = comb3m(p1[r], p2[r], p3[r]);
+                            const double pr = hypot(g.x, g.y);
                             if (pred) pred[(size_t)j * Pt + p] = pr;
                             const double rs = rv[r];
                             if (isfinite(rs) && rs > 0.0) {

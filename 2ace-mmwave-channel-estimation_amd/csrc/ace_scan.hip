@@ -6,9 +6,7 @@
 //   top_pow / top_idx = the K largest P of the realisation, total = sum of P.
 //
 // One fused kernel, one work-group (8 waves) per realisation.  Both products run on the f64 matrix cores
-// (v_mfma_f64_16x16x4_f64) in the 3M form of ace_gemm.hip (P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi);
-// Re = P1 - P2, Im = P3 - P1 - P2) with the operand maps verified there: lane l supplies A[row l & 15][k l >> 4]
-// and B[k l >> 4][col l & 15]; D lane l, reg r -> row (l >> 4) + 4 r, col l & 15.
+// (v_mfma_f64_16x16x4_f64) in the 3M form, with the helpers and the operand and result lane maps of ace_mfma.hpp.
 //
 // Tiling.  mat(x) sits in LDS for the whole launch, zero-padded to 32 x 32 (xs[i][j]).  The beam pairs are
 // walked in tiles of SC_TP = 64 precoders by SC_TQ = 64 combiners, p outer, q inner:
@@ -42,6 +40,7 @@
 // x is not degenerate.  Non-finite beams are the caller's error and are not checked.
 #include "ace_common.hpp"
 #include "ace_host.hpp"
+#include "ace_mfma.hpp"
 
 #pragma clang fp contract(off)
 
@@ -138,17 +137,11 @@ __global__ __launch_bounds__(SC_NT) void scan_kernel(int d0, int d1, int Q0, int
                 d4v p1 = d4v{0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
 #pragma unroll
                 for (int kk = 0; kk < SC_D / 4; ++kk)
-                    if (kk < nk1) {
-                        const d2 a = Bs[16 * pb * SC_ST + frow + 4 * kk], x = xs[16 * ib * SC_ST + frow + 4 * kk];
-                        p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, x.x, p1, 0, 0, 0);
-                        p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, x.y, p2, 0, 0, 0);
-                        p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x + a.y, x.x + x.y, p3, 0, 0, 0);
-                    }
+                    if (kk < nk1)
+                        mma3m(p1, p2, p3, Bs[16 * pb * SC_ST + frow + 4 * kk], xs[16 * ib * SC_ST + frow + 4 * kk]);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const double a = p1[q], c = p2[q];
-                    Ts[(16 * pb + (lane >> 4) + 4 * q) * SC_ST + 16 * ib + (lane & 15)] = make_double2(a - c, p3[q] - a - c);
-                }
+                for (int q = 0; q < 4; ++q)
+                    Ts[(16 * pb + (lane >> 4) + 4 * q) * SC_ST + 16 * ib + (lane & 15)] = comb3m(p1[q], p2[q], p3[q]);
             }
         } else {
             // ---- stage B: y = T . conj(W0 tile)^T; wave w -> combiner block w & 3, precoder blocks 2 (w >> 2) + {0, 1}
@@ -172,12 +165,7 @@ __global__ __launch_bounds__(SC_NT) void scan_kernel(int d0, int d1, int Q0, int
                         d4v p1 = d4v{0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
 #pragma unroll
                         for (int kk = 0; kk < SC_D / 4; ++kk)
-                            if (kk < nk0) {
-                                const d2 a = Ts[16 * pb * SC_ST + frow + 4 * kk], x = wf[kk];
-                                p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, x.x, p1, 0, 0, 0);
-                                p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, x.y, p2, 0, 0, 0);
-                                p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x + a.y, x.x + x.y, p3, 0, 0, 0);
-                            }
+                            if (kk < nk0) mma3m(p1, p2, p3, Ts[16 * pb * SC_ST + frow + 4 * kk], wf[kk]);
                         double cp[4];
                         int cf[4];
                         bool offer = false;
@@ -188,8 +176,8 @@ __global__ __launch_bounds__(SC_NT) void scan_kernel(int d0, int d1, int Q0, int
                             cf[g] = p * Q0 + q;
                             if (p < Q1 && q < Q0) {
                                 bad |= !isfinite(nz[g].x) || !isfinite(nz[g].y);
-                                const double a = p1[g], c = p2[g];
-                                const double yr = (a - c) + nz[g].x, yi = (p3[g] - a - c) + nz[g].y;
+                                const d2 y = comb3m(p1[g], p2[g], p3[g]);
+                                const double yr = y.x + nz[g].x, yi = y.y + nz[g].y;
                                 const double P = yr * yr + yi * yi;
                                 if (power) power[b * Q1 * Q0 + (size_t)cf[g]] = P;
                                 tot += P;

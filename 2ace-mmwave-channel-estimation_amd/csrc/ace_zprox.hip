@@ -213,11 +213,7 @@ __global__ __launch_bounds__(256) void zstep_kernel(ZArgs a) {
                     }
     #pragma unroll
                     for (int u = 0; u < 4; ++u) {   // A = E_j, B = E_j^H: the lane's operands are e and conj(e)
-                        const d2 av = ev[u];
-                        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, av.x, cr, 0, 0, 0);
-                        cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-av.y, -av.y, cr, 0, 0, 0);
-                        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, -av.y, ci, 0, 0, 0);
-                        ci = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, av.x, ci, 0, 0, 0);
+                        cmma(cr, ci, ev[u], make_double2(ev[u].x, -ev[u].y));
                     }
                 }
                 d2* part = L1;   // [4][16][16] partial tiles (exactly the L1 tile's 32 x 33 budget)
@@ -481,11 +477,7 @@ __global__ __launch_bounds__(256) void zstep_kernel(ZArgs a) {
                     d4v zr = d4v{0.0, 0.0, 0.0, 0.0}, zi = d4v{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const d2 av = wa[u], bv = ev[u];
-                        zr = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, bv.x, zr, 0, 0, 0);
-                        zr = __builtin_amdgcn_mfma_f64_16x16x4f64(-av.y, bv.y, zr, 0, 0, 0);
-                        zi = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, bv.y, zi, 0, 0, 0);
-                        zi = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, bv.x, zi, 0, 0, 0);
+                        cmma(zr, zi, wa[u], ev[u]);
                     }
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {   // lane l, reg rr -> Z_j[(l >> 4) + 4 rr][l & 15]

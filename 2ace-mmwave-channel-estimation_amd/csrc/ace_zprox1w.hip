@@ -17,6 +17,7 @@
 // (the f64 MFMA accumulator row map (l>>4)+4q equals the operand k map), and Z^T
 // puts consecutive vec(Z) indices on consecutive lanes for coalesced stores.
 #include "ace_common.hpp"
+#include "ace_mfma.hpp"
 #include "ace_zcommon.hpp"
 #include "ace_topk.hpp"
 
@@ -47,13 +48,6 @@ __device__ __forceinline__ double dpp_shl1_keep(double old, double x) {
     return __hiloint2double(hi, lo);
 }
 
-__device__ __forceinline__ void mfma_c(d2 a, d2 b, d4v& cr, d4v& ci) {  // (cr, ci) += a * b (complex)
-    cr = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, cr, 0, 0, 0);
-    cr = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.y, cr, 0, 0, 0);
-    ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, ci, 0, 0, 0);
-    ci = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.x, ci, 0, 0, 0);
-}
-
 // 16x16 complex block C = sum_k A[row][k] B[k][col] over k < 32.  fa(row, k) and
 // fb(k0, k, col) return operand values for this lane (row/col in 0..15 within the
 // block, k the absolute inner index; k0 the 4-aligned step base, compile-time after
@@ -65,7 +59,7 @@ __device__ __forceinline__ void mm16(FA fa, FB fb, d4v& cr, d4v& ci, int lane) {
 #pragma unroll
     for (int k0 = 0; k0 < 32; k0 += 4) {
         const int kk = k0 + (lane >> 4);
-        mfma_c(fa(lane & 15, kk), fb(k0, kk, lane & 15), cr, ci);
+        cmma(cr, ci, fa(lane & 15, kk), fb(k0, kk, lane & 15));
     }
 }
 
@@ -570,8 +564,8 @@ __device__ __forceinline__ void zstep1w_body(const ZArgs& a, int b) {
 #pragma unroll
             for (int s8 = 0; s8 < 8; ++s8) {
                 const d2 q = qv[I][s8];
-                mfma_c(make_double2(q.x, -q.y), T0[(4 * s8 + (lane >> 4)) * ZHS + 16 * J + (lane & 15)], cr[I][J],
-                       ci[I][J]);
+                cmma(cr[I][J], ci[I][J], make_double2(q.x, -q.y),
+                     T0[(4 * s8 + (lane >> 4)) * ZHS + 16 * J + (lane & 15)]);
             }
         }
     };
@@ -1159,7 +1153,7 @@ __device__ __forceinline__ void zstep1w_body(const ZArgs& a, int b) {
                         const int kk = 16 * K + 4 * q + (lane >> 4);
                         const d2 av = make_double2(cr[K][0][q], ci[K][0][q]);       // T[kk][16J + (lane&15)]
                         const d2 bv = T0[(16 * I + (lane & 15)) * ZHS + kk];          // Qnew[16I + c][kk]
-                        mfma_c(av, bv, zr, zi);
+                        cmma(zr, zi, av, bv);
                     }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

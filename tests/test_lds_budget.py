@@ -47,13 +47,16 @@ CASES = [
     ("bt2", "ace_heev2.hip", [r"12bt2q2_kernel", r"12bt2q1_kernel"], [32, 40, 121, 200, 256]),
 ]
 
-_REMARK = re.compile(r"remark: Function Name: (\S+)|remark:\s+LDS Size \[bytes/block\]: (\d+)")
+_REMARK = re.compile(r"remark: Function Name: (\S+)|remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)")
 
 
-def _static_lds(src: str) -> dict:
-    """Static LDS per kernel (mangled name) from the gfx950 resource report of one source."""
+def _resources(src, root=ROOT) -> dict:
+    """Every numeric line of the gfx950 resource report of one source of `root`'s csrc/, per kernel
+    (mangled name): 'VGPRs', 'AGPRs', 'TotalSGPRs', 'VGPRs Spill', 'ScratchSize', 'LDS Size', 'Occupancy', ...
+    (also the compile behind tools/kernel_resources.py)."""
+    path = pathlib.Path(root) / CSRC.relative_to(ROOT) / src
     cmd = [HIPCC, "--offload-arch=gfx950", "--offload-device-only", "-O3", "-std=c++17",
-           "-mllvm", "-amdgpu-mfma-vgpr-form=1", f"-I{ROOT / 'include'}", "-c", str(CSRC / src),
+           "-mllvm", "-amdgpu-mfma-vgpr-form=1", f"-I{pathlib.Path(root) / 'include'}", "-c", str(path),
            "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -61,10 +64,15 @@ def _static_lds(src: str) -> dict:
     for m in _REMARK.finditer(out.stderr):
         if m.group(1):
             name = m.group(1)
+            res[name] = {}
         elif name is not None:
-            res[name] = int(m.group(2))
-            name = None
+            res[name][m.group(2)] = int(m.group(3))
     return res
+
+
+def _static_lds(src: str) -> dict:
+    """Static LDS per kernel (mangled name) from the gfx950 resource report of one source."""
+    return {k: v["LDS Size"] for k, v in _resources(src).items()}
 
 
 @pytest.fixture(scope="module")
@@ -109,6 +117,18 @@ def test_no_hard_coded_budgets():
         text = p.read_text()
         assert "hipFuncSetAttribute" not in text, f"{p.name} raises an LDS limit outside lds_dyn_budget"
         assert not re.search(r"160\s*\*\s*1024\s*-", text), f"{p.name} hard-codes a 160 KiB headroom"
+
+
+def test_f64_mfma_products_live_in_one_header():
+    """The f64 matrix-core builtin and the fragment-streamed product are spelled once, in ace_mfma.hpp,
+    so kernels that must round alike (tests/test_gpu_msr.py) share the code and not a comment.  (The
+    int8 builtins, mfma_i32_*, stay with their pipelines.)"""
+    srcs = [p for p in CSRC.iterdir() if p.suffix in (".hip", ".hpp", ".cpp")]
+    for p in srcs:
+        if p.name != "ace_mfma.hpp":
+            assert "__builtin_amdgcn_mfma_f64_16x16x4f64" not in p.read_text(), f"{p.name} calls the builtin itself"
+    defs = [p.name for p in srcs if re.search(r"\bvoid\s+frag_mv\s*\(", p.read_text())]
+    assert defs == ["ace_mfma.hpp"], defs
 
 
 def test_unknown_kernel_is_an_error():
