@@ -18,6 +18,8 @@ from .beamformer import (svd_beamformer, svd_beamformer_compensation, codebook_b
 from .evaluate import evaluate_host, evaluate_batch, EvalResult  # noqa: F401
 from .rss import evaluate_rss_host, evaluate_rss_batch, dbm_to_amp, RssEval  # noqa: F401
 from .scan import beam_scan_host, beam_scan_batch, ScanResult  # noqa: F401
-from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular  # noqa: F401
+from .omp import omp_host, omp_batch, OmpResult  # noqa: F401
+from ._lib import ACE_ST_EVAL_DEGENERATE, ACE_ST_OMP_DEPENDENT  # noqa: F401
+from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular, omp, sparse  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

@@ -28,6 +28,7 @@ ACE_ST_ROLLBACK = 8
 ACE_ST_RANK_ONE = 128
 ACE_ST_EVAL_DEGENERATE = 256
 ACE_ST_RSS_SKIPPED = 512
+ACE_ST_OMP_DEPENDENT = 1024
 
 ACE_TRAIN_SHARED = 0
 ACE_TRAIN_PER_REALISATION = 1
@@ -142,6 +143,12 @@ def _load():
     lib.ace_beam_scan_batch.restype = C.c_int
     lib.ace_beam_scan_host.argtypes = [C.c_int] * 5 + [dp, dp, dp, dp, C.c_int, dp, ip, dp, dp, up]
     lib.ace_beam_scan_host.restype = C.c_int
+    lib.ace_omp_workspace_size.argtypes = [C.c_int] * 4
+    lib.ace_omp_workspace_size.restype = C.c_size_t
+    lib.ace_omp_solve_batch.argtypes = [C.c_int] * 4 + [C.c_double] + [vp] * 10 + [C.c_size_t, vp]
+    lib.ace_omp_solve_batch.restype = C.c_int
+    lib.ace_omp_solve_host.argtypes = [C.c_int] * 4 + [C.c_double, dp, dp, dp, ip, dp, ip, dp, up, dp]
+    lib.ace_omp_solve_host.restype = C.c_int
     lib.ace_spectral_init_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ace_spectral_init_host.restype = C.c_int
     lib.ace_path_counts.argtypes = [C.POINTER(C.c_int64), C.c_int]

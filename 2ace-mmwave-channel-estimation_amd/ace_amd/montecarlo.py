@@ -84,6 +84,86 @@ def vs_m(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, firs
             "columns": METRICS}
 
 
+SPARSE = ("plomp", "plomp_2s", "perfect_cs")
+
+
+def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=0, pl_maxits=4000, tol=1e-12,
+                device=None, chunk=CHUNK) -> dict:
+    """The sparse recoveries of ``sparse.py`` on ``vs_m``'s sweep: the same chunk grid, codebook, channels and noise
+    draws (``synth_problem`` at (seed, M, realisation index)), so the curves stand next to ``vs_m``'s.  Per M and
+    realisation, the four ``evaluate_batch`` columns ([nM][count][4] each, keys ``SPARSE``) of
+
+      * ``plomp``      -- ``sparse.plomp_batch`` on Phi = A AD and the squared measurements at the synth's own scale
+                          (Recover_Channel.m:25; not the B / ||B|| InferADMM sees) with ``max_atoms = mCS``: the
+                          reference's call, whose tolerance 1e-12 never stops OMP on noisy data;
+      * ``plomp_2s``   -- the same PhaseLift solution with ``max_atoms = 2 s``;
+      * ``perfect_cs`` -- ``sparse.perfect_phase_cs`` on the coherent measurements A h + w with the w whose modulus
+                          the magnitude measurements are (``synth.measurements_complex``, built on the host and
+                          uploaded), where M <= 256; NaN beyond (the OMP kernel's atom length).
+
+    ``s``: the sparsity handed to both (default L, what Vs_M.m passes).  Also returned: ``mCS`` [nM], the status
+    words of the three evaluations or-ed with the OMP stage's (``status_<key>``), the OMP stage's counts (``count_<key>``),
+    ``gain_percsi_ana`` [nM][count] (``evaluate_batch(H, H)``: the H scored is ``vs_m``'s) and the means.  Only
+    metrics, counts and status words leave the device.
+
+    Cost.  The two-stage setup runs one host SVD of Phi (M x Qt Qr) per sweep point.  PhaseLift dominates: one
+    TFOCS iteration per realisation is an eigendecomposition of an mCS x mCS matrix and two products with P, and
+    the reference's ``pl_maxits`` = 4000 at mCS around 150 makes a sweep point of 64 realisations take minutes, a
+    full 16 x 16 curve tens of minutes; lower ``pl_maxits`` to bound it and say so next to the numbers."""
+    import torch
+    from . import sparse, synth
+    from .solver import synth_problem
+    if tx != rx:
+        raise ValueError(f"vs_m_sparse needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    count, first, chunk = int(count), int(first), int(chunk)
+    if count < 1 or first < 0 or chunk < 1:
+        raise ValueError("count and chunk must be >= 1 and first >= 0")
+    s = int(L if s is None else s)
+    Ms = [int(M) for M in M_list]
+    dev = torch.device("cuda" if device is None else device)
+    n = tx * rx
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    AD = up(sparse.dictionary_2d(tx, rx)[0])
+    out = {k: np.full((len(Ms), count, 4), np.nan) for k in SPARSE}
+    stat = {k: np.zeros((len(Ms), count), np.uint32) for k in SPARSE}
+    cnt = {k: np.zeros((len(Ms), count), np.int32) for k in SPARSE}
+    percsi = np.empty((len(Ms), count), np.float64)
+    mcs = np.empty(len(Ms), np.int64)
+    end = first + count
+    for k, M in enumerate(Ms):
+        setup, Phi, Ah = None, None, synth.codebook(seed, M, n)
+        for c0 in range(first // chunk * chunk, end, chunk):
+            A, B, _, H = synth_problem(seed, c0, chunk, M, tx, rx, L=L, snr_db=snr_db, device=dev)
+            if setup is None:
+                Phi = (A[0] @ AD).contiguous()
+                setup = sparse.two_stage_setup(Phi.cpu().numpy(), s).to(dev)
+                mcs[k] = setup.mCS
+            # the synth hands out B / ||B|| (what InferADMM sees); Recover_Channel.m:25 passes the measurements as
+            # they are, and PhaseLift's trace weight lambda = 0.05 is not scale-free: undo the normalisation with
+            # ||B|| = ||H|| / ||H / ||B|| || from the host copy of the channel
+            Hh = np.stack([synth.channel(seed, c0 + b, tx, rx, L) for b in range(chunk)])
+            nb = up(np.linalg.norm(Hh, axis=1)) / torch.linalg.vector_norm(H, dim=1)
+            Braw = B * nb[:, None]
+            ts, sig = sparse.plomp_stage1(Phi, Braw * Braw, s, setup=setup, maxIts=int(pl_maxits))
+            res = {"plomp": sparse.omp_batch(ts.C, sig, ts.mCS, tol),
+                   "plomp_2s": sparse.omp_batch(ts.C, sig, min(2 * s, ts.mCS), tol)}
+            if M <= sparse.D_MAX:
+                y = np.stack([synth.measurements_complex(seed, c0 + b, Ah, Hh[b], snr_db) for b in range(chunk)])
+                res["perfect_cs"] = sparse.perfect_phase_cs(Phi, up(y), s)
+            lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+            rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
+            percsi[k, rows] = evaluate_batch(H, H, tx, rx).gain_ana[sel].cpu().numpy()
+            for name, r in res.items():
+                ev = evaluate_batch(r.channel(AD), H, tx, rx)
+                out[name][k, rows] = ev.metrics[sel].cpu().numpy()
+                # the evaluator's bits and the OMP stage's (ACE_ST_EVAL_DEGENERATE there: a non-finite PhaseLift output)
+                stat[name][k, rows] = (ev.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
+                cnt[name][k, rows] = r.count[sel].cpu().numpy()
+    return {"M": np.asarray(Ms, np.int64), "mCS": mcs, "s": s, **out, "columns": METRICS, "gain_percsi_ana": percsi,
+            **{f"status_{k}": v for k, v in stat.items()}, **{f"count_{k}": v for k, v in cnt.items()},
+            "mean": {k: v.mean(axis=1) for k, v in out.items()}}
+
+
 BASELINES = ("gain_percsi_ana", "gain_percsi_dig", "aoda_err_est", "gain_est_aoda", "gain_sweep", "aoda_err_sweep")
 
 

@@ -91,11 +91,16 @@ def paths(seed, real, L=3):
     return (u[:L] - 0.5) * 95.0, (u[L:] - 0.5) * 95.0, g / np.sqrt(np.sum(np.abs(g) ** 2))
 
 
-def measurements(seed, real, A, vecH, snr_db=30.0):
+def measurements_complex(seed, real, A, vecH, snr_db=30.0):
+    """The coherent measurement A vecH + w whose modulus ``measurements`` returns (the same noise draw)."""
     m = A.shape[0]
     sigma2 = 10.0 ** (-snr_db / 10.0)
     w = normal_pairs(seed, stream_id(ST_NOISE, real), m) * np.sqrt(sigma2 * 0.5)
-    return np.abs(A @ vecH + w)
+    return A @ vecH + w
+
+
+def measurements(seed, real, A, vecH, snr_db=30.0):
+    return np.abs(measurements_complex(seed, real, A, vecH, snr_db))
 
 
 def initial_iterate(seed, real, vecH, x0_noise=0.5):

@@ -499,6 +499,43 @@ int ace_beam_scan_host(int batch, int d0, int d1, int Q0, int Q1, const double* 
                        const double* F1, const double* noise, int K, double* top_pow, int32_t* top_idx,
                        double* total, double* power, uint32_t* status);   /* allocates, copies, synchronous */
 
+/* ---- batched orthogonal matching pursuit (the sparse stage of PLOMP and of the coherent CS benchmark) ----
+ * The reference calls OMP(C, intSoln, 1e-12) (My_TwoStage_Recovery.m) and OMP(A, y, s) (My_Conventional_CS.m);
+ * OMP.m itself belongs to the external CoSaMP_OMP toolbox and is not in the reference tree.  This is textbook
+ * OMP with both stopping rules; "a third argument below 1 is a tolerance" is this project's reading of the call
+ * sites, not a transcription.  Per realisation, against one shared dictionary:
+ *   r = y, I = {};  repeat: stop if |I| = kmax or ||r||_2 <= tol;
+ *                           j = argmax over j not in I of w_j |d_j^H r|^2   (ties: smaller j; w = colscale or 1);
+ *                           I <- I u {j};  c = argmin ||y - D_I c||_2;  r = y - D_I c
+ * D [d][N] c128 row-major (column j = atom j, shared by the batch); colscale NULL or [N] f64; Y [batch][d]
+ * c128; all DEVICE.  Outputs: idx [batch][kmax] int32 in selection order, -1 past count; coef [batch][kmax]
+ * c128 in the same order, 0 past count; count [batch] int32; resnorm [batch] f64, the final ||r||_2; status
+ * [batch] (may be NULL); x [batch][N] c128 (may be NULL), the dense solution.  workspace: at least
+ * ace_omp_workspace_size(batch, d, N, kmax) bytes of DEVICE memory (the progressive QR factors of D_I, built by
+ * modified Gram-Schmidt); ACE_ERR_WORKSPACE when NULL or shorter.  Asynchronous on stream; no allocation, no
+ * host synchronisation, no atomics.  A realisation's outputs are a function of (y_b, D, colscale, d, N, kmax,
+ * tol) alone: not of batch, of b, of x being requested, or of the stream.
+ * Limits: 1 <= d <= 256, 1 <= N <= 16384, 1 <= kmax <= min(d, N), tol >= 0, batch >= 1.  A size below 1, a
+ * kmax beyond min(d, N), a tol that is negative or NaN and a NULL D, Y, idx, coef, count or resnorm return
+ * ACE_ERR_ARG; d > 256 or N > 16384, or a refused dynamic LDS request, return ACE_ERR_UNSUPPORTED; all of it
+ * before any HIP call.  There is no second path and no CPU fallback.  ace_omp_workspace_size returns 0 for
+ * sizes outside the limits.
+ * Departures from a textbook OMP / the reference's call:
+ *   - a non-finite entry of y_b gives count 0, indices -1, resnorm 0 and ACE_ST_EVAL_DEGENERATE;
+ *   - y_b = 0, or ||y_b|| <= tol, gives count 0 and no flag;
+ *   - a selected atom whose part orthogonal to the span of the chosen atoms has norm <= 2^-26 ||d_j|| (sqrt(u):
+ *     with it kappa_2(D_I) >= 2^26 and the coefficients would keep fewer than half their digits) is NOT added;
+ *     the realisation stops there and sets ACE_ST_OMP_DEPENDENT.  An all-zero atom is dependent by that test.
+ * A non-finite entry of D or colscale is the caller's error and is not checked. */
+#define ACE_ST_OMP_DEPENDENT 1024u
+size_t ace_omp_workspace_size(int batch, int d, int N, int kmax);
+int ace_omp_solve_batch(int batch, int d, int N, int kmax, double tol, const double* D, const double* colscale,
+                        const double* Y, int32_t* idx, double* coef, int32_t* count, double* resnorm,
+                        uint32_t* status, double* x, void* workspace, size_t workspace_bytes, void* stream);
+int ace_omp_solve_host(int batch, int d, int N, int kmax, double tol, const double* D, const double* colscale,
+                       const double* Y, int32_t* idx, double* coef, int32_t* count, double* resnorm,
+                       uint32_t* status, double* x);   /* host arrays; allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
@@ -568,7 +605,8 @@ int ace_path_counts(int64_t* counts, int reset);
 
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
- * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used).  With the kernel's static LDS
+ * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used),
+ * "omp" (m = d, the atoms' length).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
 int ace_lds_request(const char* kernel, int m, size_t* bytes);
