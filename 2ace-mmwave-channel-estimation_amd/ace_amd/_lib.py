@@ -29,6 +29,9 @@ ACE_ST_RANK_ONE = 128
 ACE_ST_EVAL_DEGENERATE = 256
 ACE_ST_RSS_SKIPPED = 512
 ACE_ST_OMP_DEPENDENT = 1024
+ACE_ST_GAMP_NANBREAK = 2048
+ACE_ST_GAMP_MAXEM = 4096
+ACE_ST_GAMP_FAILED = 8192
 
 ACE_TRAIN_SHARED = 0
 ACE_TRAIN_PER_REALISATION = 1
@@ -79,6 +82,20 @@ class PipelineCfg(C.Structure):
         ("cc_frac", C.c_double),
         ("tol_rel", C.c_double),
         ("tol_abs", C.c_double),
+    ]
+
+
+class GampCfg(C.Structure):
+    """Mirror of ``ace_gamp_cfg`` (include/ace.h)."""
+    _fields_ = [
+        ("snr_db", C.c_double),
+        ("lambda0", C.c_double),
+        ("learn_lambda", C.c_int),
+        ("max_em_iter", C.c_int),
+        ("gamp_nit", C.c_int),
+        ("reserved", C.c_int),
+        ("step0", C.c_double),
+        ("gamp_tol", C.c_double),
     ]
 
 
@@ -149,6 +166,15 @@ def _load():
     lib.ace_omp_solve_batch.restype = C.c_int
     lib.ace_omp_solve_host.argtypes = [C.c_int] * 4 + [C.c_double, dp, dp, dp, ip, dp, ip, dp, up, dp]
     lib.ace_omp_solve_host.restype = C.c_int
+    gcfgp = C.POINTER(GampCfg)
+    lib.ace_gamp_cfg_default.argtypes = [gcfgp]
+    lib.ace_gamp_cfg_default.restype = None
+    lib.ace_gamp_workspace_size.argtypes = [C.c_int] * 3
+    lib.ace_gamp_workspace_size.restype = C.c_size_t
+    lib.ace_gamp_solve_batch.argtypes = [gcfgp] + [C.c_int] * 3 + [vp] * 9 + [C.c_size_t, vp]
+    lib.ace_gamp_solve_batch.restype = C.c_int
+    lib.ace_gamp_solve_host.argtypes = [gcfgp] + [C.c_int] * 3 + [dp, dp, dp, dp, dp, ip, ip, up]
+    lib.ace_gamp_solve_host.restype = C.c_int
     lib.ace_spectral_init_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ace_spectral_init_host.restype = C.c_int
     lib.ace_path_counts.argtypes = [C.POINTER(C.c_int64), C.c_int]
@@ -194,6 +220,16 @@ def default_cfg(**kw) -> AdmmCfg:
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError(f"unknown ace_admm_cfg field {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def gamp_cfg(**kw) -> GampCfg:
+    cfg = GampCfg()
+    LIB.ace_gamp_cfg_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"unknown ace_gamp_cfg field {k!r}")
         setattr(cfg, k, v)
     return cfg
 

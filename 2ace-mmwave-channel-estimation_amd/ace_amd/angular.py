@@ -23,11 +23,13 @@ KAPPA = 2.0 * np.pi * (synth.ANT_D / synth.LAMBDA)
 SEARCH_DEG = 95.0                 # the synth's angular range (Generate_Channel.m: AoD, AoA ~ U(-47.5, 47.5) deg)
 
 
-def steering(n_ant, sin_theta):
+def steering(n_ant, sin_theta, ant_d=None):
     """Array response exp(-1j kappa sin(theta) k) / sqrt(n_ant), k = 0 .. n_ant - 1, one row per entry of
-    ``sin_theta`` (Sparse_Channel_Formulation.m:86)."""
+    ``sin_theta`` (Sparse_Channel_Formulation.m:86).  ``ant_d``: the element spacing in metres (kappa = 2 pi ant_d /
+    lambda); default the synth's."""
     s = np.atleast_1d(np.asarray(sin_theta, np.float64))
-    ph = KAPPA * s[:, None] * np.arange(n_ant)[None, :]
+    kappa = KAPPA if ant_d is None else 2.0 * np.pi * (float(ant_d) / synth.LAMBDA)
+    ph = kappa * s[:, None] * np.arange(n_ant)[None, :]
     return (np.cos(ph) - 1j * np.sin(ph)) / np.sqrt(n_ant)
 
 
@@ -39,15 +41,17 @@ def grid_cut(NQ, search_deg=SEARCH_DEG):
     return g, int(np.argmin(np.abs(g + edge))), int(np.argmin(np.abs(g - edge)))
 
 
-def dictionary(n_ant, NQ=None, search_deg=SEARCH_DEG):
+def dictionary(n_ant, NQ=None, search_deg=SEARCH_DEG, ant_d=None):
     """The steering dictionary of Sparse_Channel_Formulation.m:76-93 with its position-information cut (:114-134):
     (beams [Q][n_ant], their sin grid [Q], their angles in degrees [Q]); NQ = 4 n_ant grid points over sin in
     [-1, 1) by default.  The cut is not optional: at d / lambda = 0.616 the full grid aliases (a steering vector
-    at sin theta equals the one at sin theta +- lambda / d), and a peak of the full map may sit on the alias."""
+    at sin theta equals the one at sin theta +- lambda / d), and a peak of the full map may sit on the alias.
+    ``ant_d``: the element spacing in metres (default the synth's); ``search_deg = 180`` keeps the whole grid, which
+    is what the directional driver's Searching_Area = 180 does."""
     NQ = 4 * n_ant if NQ is None else int(NQ)
     g, lo, hi = grid_cut(NQ, search_deg)
     s = g[lo:hi + 1]
-    return steering(n_ant, s), s, np.rad2deg(np.arcsin(s))
+    return steering(n_ant, s, ant_d), s, np.rad2deg(np.arcsin(s))
 
 
 _J = np.array([-1.0, -1j, 1.0, 1j, -1.0])   # exp(1j phi) on -pi : pi/2 : pi, exactly

@@ -85,10 +85,11 @@ def vs_m(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, firs
 
 
 SPARSE = ("plomp", "plomp_2s", "perfect_cs")
+SPARSE_GAMP = ("plgamp", "perfect_cs_gamp")
 
 
 def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=0, pl_maxits=4000, tol=1e-12,
-                device=None, chunk=CHUNK) -> dict:
+                device=None, chunk=CHUNK, gamp=False) -> dict:
     """The sparse recoveries of ``sparse.py`` on ``vs_m``'s sweep: the same chunk grid, codebook, channels and noise
     draws (``synth_problem`` at (seed, M, realisation index)), so the curves stand next to ``vs_m``'s.  Per M and
     realisation, the four ``evaluate_batch`` columns ([nM][count][4] each, keys ``SPARSE``) of
@@ -100,6 +101,15 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
       * ``perfect_cs`` -- ``sparse.perfect_phase_cs`` on the coherent measurements A h + w with the w whose modulus
                           the magnitude measurements are (``synth.measurements_complex``, built on the host and
                           uploaded), where M <= 256; NaN beyond (the OMP kernel's atom length).
+
+    ``gamp=True`` adds the EM-BG-GAMP baselines on the same chunk grid and draws (keys ``SPARSE_GAMP``; the keys of
+    ``SPARSE`` and their values do not change):
+
+      * ``plgamp``          -- ``Method.PLGAMP``: the PhaseLift solution ``plomp`` uses, then ``gamp.embgamp_batch`` on C
+                               with noise_power = 10^(-snr_db / 10) and the reference's OMP fallback;
+      * ``perfect_cs_gamp`` -- ``sparse.perfect_phase_cs(..., solver="embgamp")`` on ``perfect_cs``'s measurements;
+
+    with ``status_<key>`` (the evaluator's bits or-ed with the GAMP stage's) and ``em_iters_<key>`` [nM][count].
 
     ``s``: the sparsity handed to both (default L, what Vs_M.m passes).  Also returned: ``mCS`` [nM], the status
     words of the three evaluations or-ed with the OMP stage's (``status_<key>``), the OMP stage's counts (``count_<key>``),
@@ -127,6 +137,11 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     out = {k: np.full((len(Ms), count, 4), np.nan) for k in SPARSE}
     stat = {k: np.zeros((len(Ms), count), np.uint32) for k in SPARSE}
     cnt = {k: np.zeros((len(Ms), count), np.int32) for k in SPARSE}
+    keys_g = SPARSE_GAMP if gamp else ()
+    out.update({k: np.full((len(Ms), count, 4), np.nan) for k in keys_g})
+    stat.update({k: np.zeros((len(Ms), count), np.uint32) for k in keys_g})
+    emi = {k: np.zeros((len(Ms), count), np.int32) for k in keys_g}
+    noise_power = 10.0 ** (-snr_db / 10.0)
     percsi = np.empty((len(Ms), count), np.float64)
     mcs = np.empty(len(Ms), np.int64)
     end = first + count
@@ -150,6 +165,11 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
             if M <= sparse.D_MAX:
                 y = np.stack([synth.measurements_complex(seed, c0 + b, Ah, Hh[b], snr_db) for b in range(chunk)])
                 res["perfect_cs"] = sparse.perfect_phase_cs(Phi, up(y), s)
+                if gamp:
+                    res["perfect_cs_gamp"] = sparse.perfect_phase_cs(Phi, up(y), s, solver="embgamp",
+                                                                     noise_power=noise_power)
+            if gamp:
+                res["plgamp"] = sparse._gamp_stage2(ts, sig, s, noise_power, Phi.shape[1])
             lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
             rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
             percsi[k, rows] = evaluate_batch(H, H, tx, rx).gain_ana[sel].cpu().numpy()
@@ -158,10 +178,13 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
                 out[name][k, rows] = ev.metrics[sel].cpu().numpy()
                 # the evaluator's bits and the OMP stage's (ACE_ST_EVAL_DEGENERATE there: a non-finite PhaseLift output)
                 stat[name][k, rows] = (ev.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
-                cnt[name][k, rows] = r.count[sel].cpu().numpy()
+                if name in emi:
+                    emi[name][k, rows] = r.em_iters[sel].cpu().numpy()
+                else:
+                    cnt[name][k, rows] = r.count[sel].cpu().numpy()
     return {"M": np.asarray(Ms, np.int64), "mCS": mcs, "s": s, **out, "columns": METRICS, "gain_percsi_ana": percsi,
             **{f"status_{k}": v for k, v in stat.items()}, **{f"count_{k}": v for k, v in cnt.items()},
-            "mean": {k: v.mean(axis=1) for k, v in out.items()}}
+            **{f"em_iters_{k}": v for k, v in emi.items()}, "mean": {k: v.mean(axis=1) for k, v in out.items()}}
 
 
 BASELINES = ("gain_percsi_ana", "gain_percsi_dig", "aoda_err_est", "gain_est_aoda", "gain_sweep", "aoda_err_sweep")

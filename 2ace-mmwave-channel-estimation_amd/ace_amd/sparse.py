@@ -6,8 +6,13 @@ ADMM recoveries.
   * ``plomp_batch``        -- ``Method.PLOMP``: PhaseLift on P (``phaselift_batch``, unchanged), then OMP on C
                               (``omp.omp_batch``).  Recover_Channel.m:23-29 feeds it ``beams * AD`` and maps the result
                               back with ``AD * plomp_signal``: ``OmpResult.channel(AD)``.
-  * ``perfect_phase_cs``   -- ``Method.PerfectPhaseCS``: the ``OMP(A, y, s)`` branch of My_Conventional_CS.m:81 on
-                              coherent (complex) measurements.
+  * ``plgamp_batch``       -- ``Method.PLGAMP``: the same PhaseLift stage, then EM-BG-GAMP on C
+                              (``gamp.embgamp_batch``; My_TwoStage_Recovery.m:163-181), with the reference's OMP
+                              fallback where EMBGAMP would raise.  ``two_stage_batch`` returns both methods from one
+                              PhaseLift run, as the reference computes them.
+  * ``perfect_phase_cs``   -- ``Method.PerfectPhaseCS`` (My_Conventional_CS.m) on coherent (complex) measurements:
+                              ``solver="omp"`` is its ``OMP(A, y, s)`` branch (:81), ``solver="embgamp"`` its first
+                              branch, EMBGAMP with learn_lambda (:71-79).
 
 ``OMP.m`` is not in the reference tree (it belongs to the external CoSaMP_OMP toolbox); ``omp.py`` says what is
 implemented in its place.  With the reference's tolerance 1e-12 on noisy data OMP does not stop on the residual: it
@@ -26,13 +31,14 @@ from . import angular
 from .omp import D_MAX, OmpResult, omp_batch
 
 
-def dictionary_2d(tx, rx, NQ_t=None, NQ_r=None, search_deg=angular.SEARCH_DEG):
+def dictionary_2d(tx, rx, NQ_t=None, NQ_r=None, search_deg=angular.SEARCH_DEG, ant_d=None):
     """AD [tx*rx][Qt*Qr]: column u Qr + v = kron(conj(A_tx[:, u]), A_rx[:, v]), u outer and v inner, over the cut
     grids of ``angular.dictionary`` (Sparse_Channel_Formulation.m:136-143).  Row t rx + r matches the synth's vec(H)
     order (element r + rx t), so a path on the grid is one column times gain sqrt(tx rx).  Returns
-    (AD, sin grid of the tx side [Qt], sin grid of the rx side [Qr])."""
-    At, st, _ = angular.dictionary(tx, NQ_t, search_deg)   # [Qt][tx], rows a(s)
-    Ar, sr, _ = angular.dictionary(rx, NQ_r, search_deg)
+    (AD, sin grid of the tx side [Qt], sin grid of the rx side [Qr]).  ``ant_d``: the element spacing in metres
+    (default the synth's)."""
+    At, st, _ = angular.dictionary(tx, NQ_t, search_deg, ant_d)   # [Qt][tx], rows a(s)
+    Ar, sr, _ = angular.dictionary(rx, NQ_r, search_deg, ant_d)
     AD = np.conj(At)[:, None, :, None] * Ar[None, :, None, :]          # [u][v][t][r]
     return np.ascontiguousarray(AD.reshape(len(st) * len(sr), tx * rx).T), st, sr
 
@@ -104,12 +110,59 @@ def plomp_batch(Phi, meas_sq, s, *, tol=1e-12, max_atoms=None, setup=None, **pl_
     return omp_batch(ts.C, sig, kmax, tol)
 
 
-def perfect_phase_cs(Phi, y_complex, s) -> OmpResult:
-    """``Method.PerfectPhaseCS``: sparse recovery from coherent measurements y = Phi x + w.  This is the
-    ``OMP(A, y, s)`` branch of My_Conventional_CS.m:81, i.e. the reference's fallback: the EM-GAMP solver it tries
-    first (EMBGAMP, an external package) is not built here.  kmax = s, tol = 0.  The kernel takes atoms of length
-    up to 256, so it needs m = Phi.shape[0] <= 256."""
+def _gamp_stage2(ts, sig, s, noise_power, n):
+    """Stage 2 of PLGAMP on a stage-1 result: EMBGAMP(intSoln, C, optEM) with SNRdB = 10 log10(1 / noise_power),
+    lambda = s / n, learn_lambda off; realisations the reference's try would leave through its catch
+    (ACE_ST_GAMP_FAILED) receive OMP(C, intSoln, 1e-12), scattered into xhat.  (Looking for such realisations reads
+    one flag back from the device.)"""
+    import torch
+    from .gamp import embgamp_batch
+    res = embgamp_batch(ts.C, sig, 10.0 * math.log10(1.0 / float(noise_power)), s / n)
+    failed = res.failed
+    if bool(failed.any()):
+        fb = omp_batch(ts.C, sig, ts.mCS, 1e-12, want_x=True)
+        res.xhat = torch.where(failed[:, None], fb.x, res.xhat)
+    return res
+
+
+def plgamp_batch(Phi, meas_sq, s, noise_power, *, setup=None, **pl_kw):
+    """``Method.PLGAMP`` (My_TwoStage_Recovery.m:163-181) for a batch: stage 1 as ``plomp_batch`` (``plomp_stage1``),
+    stage 2 ``embgamp_batch(C, intSoln, 10 log10(1 / noise_power), s / n)``.  Returns the ``GampResult`` (xhat over
+    the n columns of Phi; its ``channel(AD)`` is ``AD * plgamp_signal``); a realisation flagged ACE_ST_GAMP_FAILED
+    carries the reference's fallback, ``omp_batch(C, intSoln, mCS, 1e-12)``, and keeps the flag."""
+    ts, sig = plomp_stage1(Phi, meas_sq, s, setup=setup, **pl_kw)
+    return _gamp_stage2(ts, sig, s, noise_power, Phi.shape[1])
+
+
+def two_stage_batch(Phi, meas_sq, s, noise_power, *, tol=1e-12, max_atoms=None, setup=None, **pl_kw):
+    """Both second stages on one PhaseLift run, as My_TwoStage_Recovery.m computes them: (``plomp_batch``'s
+    OmpResult, ``plgamp_batch``'s GampResult)."""
+    ts, sig = plomp_stage1(Phi, meas_sq, s, setup=setup, **pl_kw)
+    kmax = ts.mCS if max_atoms is None else min(int(max_atoms), ts.mCS)
+    return omp_batch(ts.C, sig, kmax, tol), _gamp_stage2(ts, sig, s, noise_power, Phi.shape[1])
+
+
+def perfect_phase_cs(Phi, y_complex, s, *, solver="omp", noise_power=None):
+    """``Method.PerfectPhaseCS``: sparse recovery from coherent measurements y = Phi x + w (My_Conventional_CS.m).
+    ``solver="omp"`` (the default) is the function's ``OMP(A, y, s)`` branch (:81), the fallback of its try: kmax = s,
+    tol = 0; it returns an ``OmpResult``.  ``solver="embgamp"`` is its first branch (:71-79): EMBGAMP from the GAMP
+    package the reference vendors, with SNRdB = 10 log10(1 / noise_power), lambda = s / n and learn_lambda on; it
+    returns a ``GampResult``, and realisations flagged ACE_ST_GAMP_FAILED carry the OMP branch's solution, as the
+    reference's catch gives.  Both kernels take atoms of length up to 256, so m = Phi.shape[0] <= 256."""
     m, n = Phi.shape
     if m > D_MAX:
-        raise ValueError(f"perfect_phase_cs: Phi {m} x {n} has m > {D_MAX}, the OMP kernel's largest atom length")
-    return omp_batch(Phi, y_complex, int(s), 0.0)
+        raise ValueError(f"perfect_phase_cs: Phi {m} x {n} has m > {D_MAX}, the sparse kernels' largest atom length")
+    if solver == "omp":
+        return omp_batch(Phi, y_complex, int(s), 0.0)
+    if solver != "embgamp":
+        raise ValueError(f"solver must be 'omp' or 'embgamp', got {solver!r}")
+    if noise_power is None:
+        raise ValueError("solver='embgamp' needs noise_power (optEM.SNRdB = 10 log10(1 / noise_power))")
+    import torch
+    from .gamp import embgamp_batch
+    res = embgamp_batch(Phi, y_complex, 10.0 * math.log10(1.0 / float(noise_power)), s / n, learn_lambda=True)
+    failed = res.failed
+    if bool(failed.any()):
+        fb = omp_batch(Phi, y_complex, int(s), 0.0, want_x=True)
+        res.xhat = torch.where(failed[:, None], fb.x, res.xhat)
+    return res

@@ -107,6 +107,7 @@ int ace_lds_request(const char* kernel, int m, size_t* bytes) {
     else if (k == "bt2") *bytes = heev2_request_bytes(m, 2);
     else if (k == "scan") *bytes = scan_request_bytes();
     else if (k == "omp") *bytes = omp_request_bytes(m);
+    else if (k == "gamp") *bytes = gamp_request_bytes(m);
     else return fail(ACE_ERR_ARG, "unknown kernel '%s'", kernel);
     return ACE_OK;
 }

@@ -287,6 +287,7 @@ size_t hetrd_request_bytes(int d, int blk);  // ... of hetrd_kernel (blk = 0) / 
 size_t heev2_request_bytes(int d, int which);   // ... of he2hb_kernel (0), hb2st_kernel (1), bt2_kernel (2)
 size_t scan_request_bytes();                 // ... of scan_kernel (the same at every shape)
 size_t omp_request_bytes(int d);             // ... of omp_kernel at atom length d
+size_t gamp_request_bytes(int d);            // ... of gamp_kernel at atom length d
 
 // ------------------------------------------------------------------ launchers
 // GEMM (MFMA f64) with a shared complex LHS over a batch of realisation vectors:

@@ -536,6 +536,62 @@ int ace_omp_solve_host(int batch, int d, int N, int kmax, double tol, const doub
                        const double* Y, int32_t* idx, double* coef, int32_t* count, double* resnorm,
                        uint32_t* status, double* x);   /* host arrays; allocates, copies, synchronous */
 
+/* ---- batched EM-BG-GAMP (the sparse stage of PLGAMP and the first branch of My_Conventional_CS.m) ----------
+ * EMBGAMP(y, D, optEM) of the reference's vendored GAMP package (3rd_software_component/GAMP/trunk/code:
+ * EMGMAMP/EMBGAMP.m -> EMGMAMP/EMGMAMP.m, main/gampEst.m, CAwgnEstimIn, CAwgnEstimOut, SparseScaEstim,
+ * EMGMAMP/CBG_update.m, set_initsBG.m; MATLAB's genpath puts EMGMAMP/ ahead of EMGMAMPnew/), restated for a batch
+ * of independent realisations (T = 1 column each) against one shared dictionary: expectation-maximisation over a
+ * Bernoulli-Gaussian prior (lambda, phi; theta = 0) and the noise variance psi around generalised approximate
+ * message passing with adaptive damping.  One launch runs every EM iteration, every GAMP iteration and the final
+ * GAMP call (csrc/ace_gamp.hip states the iteration and the reference's quirks it keeps).
+ * cfg: the two option sets the reference uses differ in learn_lambda only --
+ *   PLGAMP (My_TwoStage_Recovery.m:165-172): learn_lambda 0;  My_Conventional_CS.m:71-77: learn_lambda 1;
+ *   both: SNRdB given (capped at 100), lambda0 = s / n, maxEMiter 200, robust_gamp (nit 25, step 0.1), tol 1e-5.
+ * max_em_iter = 0 skips the EM loop: one GAMP call from a cold start (the kernel-level tests' handle).
+ * D [d][N] c128 row-major, Y [batch][d] c128, DEVICE.  Outputs: xhat [batch][N] c128; xvar [batch][N] f64 (may be
+ * NULL); params [batch][3] f64 = lambda, phi, psi at exit; em_iters [batch] int32, the EM iterations started; trace
+ * (may be NULL) [batch][max_em_iter + 1][2] int32, per gampEst call its iterations and the bit mask of its passed
+ * iterations (bit it - 1), the final call in slot em_iters, unused slots 0; status [batch] (may be NULL).
+ * workspace: ace_gamp_workspace_size(batch, d, N) bytes of DEVICE memory (the N-long and d-long state vectors:
+ * 144 B per atom and 112 B per row, per realisation rounded up to 16); ACE_ERR_WORKSPACE when NULL or shorter.
+ * Asynchronous on stream; no allocation, no host synchronisation, no atomics.  A realisation's outputs are a
+ * function of (y_b, D, cfg, d, N) alone.
+ * Limits: 1 <= d <= 256, 1 <= N <= 16384, batch >= 1, 0 < lambda0 <= 1, max_em_iter >= 0, 1 <= gamp_nit <= 31,
+ * 0 < step0 <= 1, gamp_tol >= 0, snr_db finite; a NULL cfg, D, Y, xhat, params or em_iters and a value outside
+ * these return ACE_ERR_ARG, d > 256 or N > 16384 or a refused dynamic LDS request ACE_ERR_UNSUPPORTED, all before
+ * any HIP call.  ace_gamp_workspace_size returns 0 for sizes outside the limits.
+ * Status:
+ *   ACE_ST_GAMP_NANBREAK  the EM loop left through EMGMAMP.m:320 (a GAMP call with a single passed iteration leaves
+ *                         rhat NaN); the final call still ran, from the entry state of the call that broke
+ *                         (EMGMAMP.m breaks before that call's warm start is taken);
+ *   ACE_ST_GAMP_MAXEM     the EM loop left at max_em_iter without meeting its tolerance;
+ *   ACE_ST_GAMP_FAILED    the reference would raise, and its callers' catch falls back to OMP: xhat is zeroed.
+ *                         Reachable with these options: CAwgnEstimOut's assert(wvar >= 0) (psi NaN or negative);
+ *                         CAwgnEstimIn's assert(var0 > 0) on the initial phi (y = 0, or ||y||^2 overflowing); the NaN
+ *                         break in the first EM iteration (the post-loop update reads an unassigned Shat);
+ *   ACE_ST_EVAL_DEGENERATE  a non-finite entry of y_b: zeros, em_iters 0. */
+#define ACE_ST_GAMP_NANBREAK 2048u
+#define ACE_ST_GAMP_MAXEM 4096u
+#define ACE_ST_GAMP_FAILED 8192u
+typedef struct ace_gamp_cfg {
+    double snr_db;      /* optEM.SNRdB: initialises psi = ||y||^2 / (d (1 + 10^(min(100, SNRdB) / 10))) */
+    double lambda0;     /* optEM.lambda: the sparsity rate, s / n in both call sites */
+    int learn_lambda;   /* optEM.learn_lambda */
+    int max_em_iter;    /* optEM.maxEMiter (200); 0: no EM loop, one cold GAMP call */
+    int gamp_nit;       /* optGAMP.nit (25 with robust_gamp) */
+    int reserved;
+    double step0;       /* optGAMP.step (0.1 with robust_gamp) */
+    double gamp_tol;    /* optGAMP.tol (1e-5) */
+} ace_gamp_cfg;
+void ace_gamp_cfg_default(ace_gamp_cfg* cfg);   /* the PLGAMP set; snr_db 0, lambda0 0 (the caller's to set) */
+size_t ace_gamp_workspace_size(int batch, int d, int N);
+int ace_gamp_solve_batch(const ace_gamp_cfg* cfg, int batch, int d, int N, const double* D, const double* Y,
+                         double* xhat, double* xvar, double* params, int32_t* em_iters, int32_t* trace,
+                         uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int ace_gamp_solve_host(const ace_gamp_cfg* cfg, int batch, int d, int N, const double* D, const double* Y,
+                        double* xhat, double* xvar, double* params, int32_t* em_iters, int32_t* trace,
+                        uint32_t* status);   /* host arrays; allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
@@ -606,7 +662,7 @@ int ace_path_counts(int64_t* counts, int reset);
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
  * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used),
- * "omp" (m = d, the atoms' length).  With the kernel's static LDS
+ * "omp", "gamp" (m = d, the atoms' length).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
 int ace_lds_request(const char* kernel, int m, size_t* bytes);
