@@ -23,5 +23,6 @@ from .gamp import embgamp_host, embgamp_batch, GampResult  # noqa: F401
 from ._lib import ACE_ST_EVAL_DEGENERATE, ACE_ST_OMP_DEPENDENT  # noqa: F401
 from ._lib import ACE_ST_GAMP_NANBREAK, ACE_ST_GAMP_MAXEM, ACE_ST_GAMP_FAILED, GampCfg, gamp_cfg  # noqa: F401
 from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular, omp, gamp, sparse  # noqa: F401
+from . import stages  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

@@ -99,6 +99,24 @@ class GampCfg(C.Structure):
     ]
 
 
+_dp, _ip, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_ubyte)
+
+
+class StageArgs(C.Structure):
+    """Mirror of ``ace_stage_args`` (include/ace.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("op", "row_mode", "batch", "n", "m", "r", "nc", "mt", "count", "ld", "col",
+                                          "first", "scatter", "isentinel")]
+                + [("or_mask", C.c_uint32), ("bit", C.c_uint32), ("len", C.c_int64)]
+                + [(k, C.c_double) for k in ("mu0", "tol_abs", "value", "sentinel")]
+                + [(k, _dp) for k in ("X", "Y", "P0", "B", "S", "g", "M", "A", "G", "geinv", "q", "qmax", "Xmax",
+                                      "Ymax", "anorm", "bnorm", "optX", "optY", "Zb1", "Zb2", "Yb1", "Yb2", "src",
+                                      "state")]
+                + [(k, _ip) for k in ("flags", "rows", "idx", "isrc", "idst")]
+                + [("mask", _bp), ("bsrc", _bp)]
+                + [(k, _dp) for k in ("Xo", "Yo", "Mo", "No", "qo", "state_out")]
+                + [("iout", _ip), ("flags_out", _ip), ("bout", _bp)])
+
+
 def _load():
     if not LIB_PATH.exists():
         raise ImportError(
@@ -181,6 +199,8 @@ def _load():
     lib.ace_path_counts.restype = C.c_int
     lib.ace_lds_request.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_size_t)]
     lib.ace_lds_request.restype = C.c_int
+    lib.ace_stage_host.argtypes = [C.POINTER(StageArgs)]
+    lib.ace_stage_host.restype = C.c_int
     lib.ace_last_error.argtypes = []
     lib.ace_last_error.restype = C.c_char_p
     lib.ace_version.argtypes = []

@@ -707,9 +707,13 @@ void launch_flag_bits(int count, const unsigned char* flag, int* dst, unsigned b
 }
 void launch_part_geinv(int nb, const PartRows& pr, const double* G, double* geinv, int* status, hipStream_t st) {
     const int te = pr.m - pr.mt;
-    if (nb > 0 && te > 0)
-        hipLaunchKernelGGL(part_geinv_kernel, dim3(nb), dim3(256), (size_t)te * te * 16, st, pr, G, geinv, status);
+    if (nb <= 0 || te <= 0) return;
+    // te x te c128 in LDS: past the 64 KiB default from te = 65 on (147456 B at PART_MAXTE)
+    const size_t lds = part_geinv_request_bytes(te);
+    if (!lds_fits(reinterpret_cast<const void*>(&part_geinv_kernel), "part_geinv_kernel", lds)) return;
+    hipLaunchKernelGGL(part_geinv_kernel, dim3(nb), dim3(256), lds, st, pr, G, geinv, status);
 }
+size_t part_geinv_request_bytes(int te) { return (size_t)te * te * sizeof(d2); }
 void launch_part_gfix(int nb, int r, const PartRows& pr, const double* G, double* g, const RealState* rs,
                       hipStream_t st) {
     if (nb > 0) hipLaunchKernelGGL(part_gfix_kernel, dim3(nb), dim3(256), 0, st, r, pr, G, g, rs);

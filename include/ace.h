@@ -34,6 +34,10 @@
  *                            generate_sensing_matrix/Generate_Sensing_Matrix.m:85-122
  *                            ('Random_Phase_State') and
  *                            generate_measurement/Generate_Measurement.m:67-136.
+ *  ace_stage_host         <- test entry: one kernel of the r-column stages and of the pipeline around
+ *                            them (init :296-310, ArgMinY :511-533, opt_X / opt_Y :384-385, the
+ *                            rotation :263-264, quality :68, best of restarts :79-83, rollback and
+ *                            rescale :93-107, the per-realisation partitions' Schur form) on host arrays.
  *
  * Conventions
  *  - Complex values are complex128, interleaved (re, im) doubles.
@@ -357,6 +361,72 @@ typedef struct ace_zprox_args {
     int32_t *flags_out, *tkcnt;
 } ace_zprox_args;
 int ace_zprox_host(const ace_zprox_args* args);
+
+/* ---- test entry: one kernel of the r-column stages / of the pipeline around them on host arrays --------
+ * The kernels of csrc/ace_stage.hip on their own (tests/test_gpu_stage.py compares them with longdouble
+ * transcriptions of inferLowRankV4_multi.m, tests/stage_ref.py).  The entry uploads the operands, fills every output
+ * with `sentinel` (int32 outputs: `isentinel`, byte outputs: its low byte), fills one control block per realisation
+ * from state / flags where the kernel reads one (every other field zero; both NULL: zeros, mu = 1) and calls the
+ * launcher a solve calls.  All arrays are HOST; c128 as (re, im) doubles.  Outputs may be NULL.
+ *   state [batch][ACE_SG_NSTATE]: mu, last_res, opt_obj, nB, obj2, nAX2, nY2, nJM2, dY2
+ *   flags [batch][ACE_SG_NFLAG]:  iters, done, status, objcol, optsrc, optysrc
+ * op (sizes; inputs -> outputs):
+ *   INIT_R       row_mode, batch, n, m, r, mu0; X (X0) [b][r][n], P0 (= A X0) [b][r][m], B [b][m], mask [b][m]
+ *                (optional, 1 on train rows) -> Xo, No [b][r][n], Yo, Mo [b][r][m], state_out, flags_out
+ *   YSTEP_R      row_mode, batch, m, r; S, g, M, Y (Y_old) [b][r][m], B, mask, state (mu), flags (done)
+ *                -> Yo (Y_new), Mo (M in place), state_out, flags_out
+ *   FINALIZE_R   batch, n, m, r, nc; optX [b][nc][n], optY [b][nc][m], X (current) [b][r][n], Y [b][r][m], Zb1, Zb2,
+ *                Yb1, Yb2 (optional, as optX / optY), state, flags -> Xo [b][nc][n], Yo [b][nc][m], qo [b] (mu),
+ *                iout [b][2] (iters, status)
+ *   GRAM_ROTATE  batch, n, r; X [b][r][n], idst [b] (optional status in) -> Xo, iout [b] (status)
+ *   QUALITY      batch, n, count (= m_te, may be 0); A [count][n], X [b][n], B [b][count] -> qo [b]
+ *   PART_QUALITY batch, n, m, mt; A [m][n], X [b][n], B [b][m], rows [b][m] -> qo [b]
+ *   KEEP_BEST    batch, n, m, first; q, qmax [b], X [b][n], Y [b][m], Xmax, Ymax (optional: sentinel)
+ *                -> qo (qmax), Xo (Xmax), Yo (Ymax)
+ *   FINISH       batch, n, m, mt; q (last quality) [b], X [b][n], Y [b][m], Xmax [b][n], Ymax [b][mt], anorm [1],
+ *                bnorm [b], idst [b] (optional status in) -> Xo [b][n], Yo [b][m], iout [b] (status)
+ *   PART_GEINV   batch, m, mt; G [m][m], rows, idst (optional status in) -> Xo [b][te][te], iout [b] (status)
+ *   PART_GFIX    batch, m, mt, r; G, geinv [b][te][te], g (= G T~) [b][r][m], rows, mask [b][m], flags (optional: done)
+ *                -> Yo [b][r][m] (g in place)
+ *   PART_EXPAND  batch, m, mt, r; Y [b][r][mt], rows -> Yo [b][r][m];  PART_COMPACT the other way
+ *   ANORM        m, n, tol_abs; A [m][n] -> qo [1]
+ *   BNORM        batch, m, tol_abs; B [b][m] -> qo [b] (B_norm), Xo [b][m] doubles (B / B_norm)
+ *   GATHER_ROWS  m, n, count; A [m][n], idx [count], anorm [1] -> Xo [count][n]
+ *   GATHER_B     batch, m, count; B [b][m], idx [count] -> qo [b][count]
+ *   MOVE_ROWS    count, len, m, scatter; src [scatter ? count : m][len] doubles, idx [count] (into the m rows of the
+ *                other side) -> qo [scatter ? m : count][len];  MOVE_BYTES the same on bsrc -> bout
+ *   PUT_COL      count, m, ld, col, or_mask; isrc [count], idx (optional, distinct), idst [m][ld] (optional) -> iout
+ *   FLAG_BITS    count, m, bit; bsrc [count] flags, idst [m] (optional) -> iout [m]
+ *   FILL         len, m, value -> qo [m] (the first len elements)
+ * Checked before any HIP call, with the argument's name in ace_last_error(): ACE_ERR_ARG for a NULL array, a size
+ * out of range, rows that are no permutation of 0 .. m-1 or an idx outside its array; ACE_ERR_UNSUPPORTED for
+ * r > 32 and for m - mt > 96 test rows.  Synchronous; allocates its own device memory. */
+enum {
+    ACE_STAGE_INIT_R = 0, ACE_STAGE_YSTEP_R, ACE_STAGE_FINALIZE_R, ACE_STAGE_GRAM_ROTATE, ACE_STAGE_QUALITY,
+    ACE_STAGE_PART_QUALITY, ACE_STAGE_KEEP_BEST, ACE_STAGE_FINISH, ACE_STAGE_PART_GEINV, ACE_STAGE_PART_GFIX,
+    ACE_STAGE_PART_EXPAND, ACE_STAGE_PART_COMPACT, ACE_STAGE_ANORM, ACE_STAGE_BNORM, ACE_STAGE_GATHER_ROWS,
+    ACE_STAGE_GATHER_B, ACE_STAGE_MOVE_ROWS, ACE_STAGE_MOVE_BYTES, ACE_STAGE_PUT_COL, ACE_STAGE_FLAG_BITS,
+    ACE_STAGE_FILL, ACE_STAGE_NOPS
+};
+#define ACE_SG_NSTATE 9
+#define ACE_SG_NFLAG 6
+typedef struct ace_stage_args {
+    int32_t op, row_mode, batch, n, m, r, nc, mt;
+    int32_t count, ld, col, first, scatter, isentinel;
+    uint32_t or_mask, bit;
+    int64_t len;
+    double mu0, tol_abs, value, sentinel;
+    const double *X, *Y, *P0, *B, *S, *g, *M, *A, *G, *geinv;
+    const double *q, *qmax, *Xmax, *Ymax, *anorm, *bnorm, *optX, *optY, *Zb1, *Zb2, *Yb1, *Yb2, *src;
+    const double* state;
+    const int32_t* flags;
+    const int32_t *rows, *idx, *isrc, *idst;
+    const unsigned char *mask, *bsrc;
+    double *Xo, *Yo, *Mo, *No, *qo, *state_out;
+    int32_t *iout, *flags_out;
+    unsigned char* bout;
+} ace_stage_args;
+int ace_stage_host(const ace_stage_args* args);
 
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(

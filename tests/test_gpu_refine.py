@@ -207,14 +207,22 @@ def test_per_realisation_partitions_match_one_by_one(gpu):
     """Per-realisation partitions in one batch (m-space stages, Schur-form G_t) against each realisation
     solved alone on its own partition (the shared-A_t path with K_t, G_t formed directly): 16-ant,
     m = 64 (f64 applies) and 32-ant, m = 256, batch 16 (int8 digit-plane applies, 320 vectors): equal
-    stage iteration counts and rollback flags, X within 1e-8 (different summation orders only)."""
+    stage iteration counts and rollback flags, X within 1e-8 (different summation orders only).
+
+    Also 16-ant, m = 128, batch 5 at cc_frac 0.5 (64 test rows: the largest G_ee^-1 inside the default 64 KiB of
+    dynamic LDS, streamed by part_gfix) and 0.25 (96 test rows: PART_MAXTE, 147456 B of dynamic LDS).  maxiter = 500:
+    under a 1e-15 relative change of B the numpy oracle's X (O.infer_low_rank_pipeline at this shape, these seeds)
+    moves by at most 4.97e-11 (cc_frac 0.5) and 1.52e-12 (0.25), the same at every horizon from 60 to 500 iterations
+    (all stages have converged by then), so the default horizon is the longest and 1e-8 has a hundredfold margin."""
     from ace_amd import infer_low_rank_pipeline_host, synth, draw_partitions
-    for ant, m, batch, maxiter in ((16, 64, 5, 500), (32, 256, 16, 150)):
-        A, B, _, _ = synth.problem(4151 + ant, 0, batch, m, ant, ant)
-        tr = draw_partitions(np.random.default_rng(4151 + ant), m, 3, batch=batch)
-        full = infer_low_rank_pipeline_host(A[0], B, ant, ant, tr, maxiter=maxiter)
+    cases = [(16, 64, 5, 500, 0.95, 4151 + 16), (32, 256, 16, 150, 0.95, 4151 + 32),
+             (16, 128, 5, 500, 0.5, 4151 + 16 + 50), (16, 128, 5, 500, 0.25, 4151 + 16 + 25)]
+    for ant, m, batch, maxiter, cc_frac, seed in cases:
+        A, B, _, _ = synth.problem(seed, 0, batch, m, ant, ant)
+        tr = draw_partitions(np.random.default_rng(seed), m, 3, cc_frac=cc_frac, batch=batch)
+        full = infer_low_rank_pipeline_host(A[0], B, ant, ant, tr, maxiter=maxiter, cc_frac=cc_frac)
         for b in range(batch):
-            one = infer_low_rank_pipeline_host(A[0], B[b:b + 1], ant, ant, tr[b], maxiter=maxiter)
+            one = infer_low_rank_pipeline_host(A[0], B[b:b + 1], ant, ant, tr[b], maxiter=maxiter, cc_frac=cc_frac)
             assert np.array_equal(one.stage_iters[0], full.stage_iters[b]), (ant, b, one.stage_iters, full.stage_iters[b])
             assert one.rolled_back[0] == full.rolled_back[b] and one.rank_one[0] == full.rank_one[b]
             assert O.phase_aligned_rel_err(full.X[b], one.X[0]) <= 1e-8, (ant, b)

@@ -45,6 +45,9 @@ CASES = [
     ("he2hb", "ace_heev2.hip", [r"12he2hb_kernel"], [32, 40, 121, 200, 256]),
     ("hb2st", "ace_heev2.hip", [r"12hb2st_kernel"], [32, 40, 121, 200, 256]),
     ("bt2", "ace_heev2.hip", [r"12bt2q2_kernel", r"12bt2q1_kernel"], [32, 40, 121, 200, 256]),
+    # G_ee^-1 of the per-realisation partitions (the size is te, the test rows): te x te c128, past the 64 KiB
+    # default from te = 65 on, 147456 B at PART_MAXTE = 96
+    ("part_geinv", "ace_stage.hip", [r"17part_geinv_kernel"], [13, 48, 64, 65, 96]),
 ]
 
 _REMARK = re.compile(r"remark: Function Name: (\S+)|remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)")
