@@ -255,38 +255,24 @@ int solve_odd_tx(const ace_admm_cfg* cfg, int batch, int m, int n, int tx, int r
     const int txp = tx + 1, np = txp * rx, r = cols(cfg), R = cfg->scale_by_row ? r : 1;
     const size_t arows = (size_t)(cfg->a_shared ? 1 : batch) * m * rx, xrows = (size_t)batch * r * rx,
                  orows = (size_t)batch * R * rx, ws = ace_admm_workspace_size(cfg, batch, m, np) + 4096;
-    void *dA = nullptr, *dX0 = nullptr, *dX = nullptr, *dW = nullptr;
-    hipError_t e = hipMalloc(&dA, arows * txp * 16);
-    if (e == hipSuccess) e = hipMalloc(&dX0, xrows * txp * 16);
-    if (e == hipSuccess) e = hipMalloc(&dX, orows * txp * 16);
-    if (e == hipSuccess) e = hipMalloc(&dW, ws);
-    auto release = [&]() {   // (the solve's work on st must finish before its buffers go)
-        (void)hipStreamSynchronize(st);
-        for (void* q : {dA, dX0, dX, dW})
-            if (q) (void)hipFree(q);
-    };
+    DevScope d;
+    d.borrow(st);   // (the solve's work on st must finish before its buffers go)
+    double *dA, *dX0, *dX;
+    char* dW;
+    ACE_TRY(d.alloc(&dA, 2 * arows * txp));
+    ACE_TRY(d.alloc(&dX0, 2 * xrows * txp));
+    ACE_TRY(d.alloc(&dX, 2 * orows * txp));
+    ACE_TRY(d.alloc(&dW, ws));
     // [rows][tx] runs of complex entries -> [rows][tx + 1] with a zero last entry
-    if (e == hipSuccess) e = hipMemsetAsync(dA, 0, arows * txp * 16, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dX0, 0, xrows * txp * 16, st);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(dA, (size_t)txp * 16, A, (size_t)tx * 16, (size_t)tx * 16, arows, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(dX0, (size_t)txp * 16, X0, (size_t)tx * 16, (size_t)tx * 16, xrows, hipMemcpyDeviceToDevice,
-                             st);
-    if (e != hipSuccess) {
-        release();
-        return fail(ACE_ERR_HIP, "odd-tx padding: %s", hipGetErrorString(e));
-    }
-    int rc = solve_core(cfg, batch, m, np, txp, rx, tx, n, (const double*)dA, B, (const double*)dX0, (double*)dX, Yo,
-                        iters, status, mu_out, dW, ws, st);
-    if (rc == ACE_OK &&
-        (e = hipMemcpy2DAsync(Xo, (size_t)tx * 16, dX, (size_t)txp * 16, (size_t)tx * 16, orows, hipMemcpyDeviceToDevice,
-                              st)) != hipSuccess)
-        rc = fail(ACE_ERR_HIP, "odd-tx unpadding: %s", hipGetErrorString(e));
-    const std::string keep = g_err;
-    release();
-    g_err = keep;
-    return rc;
+    ACE_HIP(hipMemsetAsync(dA, 0, arows * txp * 16, st));
+    ACE_HIP(hipMemsetAsync(dX0, 0, xrows * txp * 16, st));
+    ACE_HIP(hipMemcpy2DAsync(dA, (size_t)txp * 16, A, (size_t)tx * 16, (size_t)tx * 16, arows, hipMemcpyDeviceToDevice, st));
+    ACE_HIP(hipMemcpy2DAsync(dX0, (size_t)txp * 16, X0, (size_t)tx * 16, (size_t)tx * 16, xrows, hipMemcpyDeviceToDevice,
+                             st));
+    ACE_TRY(solve_core(cfg, batch, m, np, txp, rx, tx, n, dA, B, dX0, dX, Yo, iters, status, mu_out, dW, ws, st));
+    ACE_HIP(hipMemcpy2DAsync(Xo, (size_t)tx * 16, dX, (size_t)txp * 16, (size_t)tx * 16, orows, hipMemcpyDeviceToDevice,
+                             st));
+    return ACE_OK;
 }
 }  // namespace
 
@@ -354,62 +340,38 @@ int ace_admm_solve_host(const ace_admm_cfg* cfg, int batch, int m, int n, int tx
     int rc = validate(cfg, batch, m, n, tx, rx);
     if (rc) return rc;
     const int r = cols(cfg), R = cfg->scale_by_row ? r : 1;
-    const size_t nA = (size_t)(cfg->a_shared ? 1 : batch) * m * n * 16;
-    const size_t nB = (size_t)batch * m * 8, nX0 = (size_t)batch * r * n * 16, nX = (size_t)batch * R * n * 16,
-                 nY = (size_t)batch * R * m * 16;
+    // element counts (doubles; a complex entry is two)
+    const size_t nA = (size_t)(cfg->a_shared ? 1 : batch) * m * n * 2;
+    const size_t nB = (size_t)batch * m, nX0 = (size_t)batch * r * n * 2, nX = (size_t)batch * R * n * 2,
+                 nY = (size_t)batch * R * m * 2;
     const size_t ws = ace_admm_workspace_size(cfg, batch, m, n) + 4096;
-    std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes, void** p) -> hipError_t {
-        hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    };
-    auto cleanup = [&]() {
-        for (void* p : bufs) (void)hipFree(p);
-        bufs.clear();
-    };
-    void *dA, *dB, *dX0, *dX, *dY, *dW, *dI, *dS, *dM, *dR = nullptr;
-    hipError_t e = hipSuccess;
-    if ((e = dalloc(nA, &dA)) || (e = dalloc(nB, &dB)) || (e = dalloc(nX0, &dX0)) || (e = dalloc(nX, &dX)) ||
-        (e = dalloc(nY, &dY)) || (e = dalloc(ws, &dW)) || (e = dalloc(4 * (size_t)batch, &dI)) ||
-        (e = dalloc(4 * (size_t)batch, &dS)) || (e = dalloc(8 * (size_t)batch, &dM)) ||
-        (cfg->rank_one && (e = dalloc((size_t)batch, &dR)))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-    }
-#define ACE_HIPC(call)                                                                               \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            cleanup();                                                                               \
-            return fail(ACE_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));                        \
-        }                                                                                            \
-    } while (0)
-    ACE_HIPC(hipMemcpy(dA, A, nA, hipMemcpyHostToDevice));
-    ACE_HIPC(hipMemcpy(dB, B, nB, hipMemcpyHostToDevice));
-    ACE_HIPC(hipMemcpy(dX0, X0, nX0, hipMemcpyHostToDevice));
+    DevScope d;
+    double *dA, *dB, *dX0, *dX, *dY, *dM;
+    char* dW;
+    int32_t* dI;
+    uint32_t* dS;
+    ACE_TRY(d.put(&dA, A, nA));
+    ACE_TRY(d.put(&dB, B, nB));
+    ACE_TRY(d.put(&dX0, X0, nX0));
+    ACE_TRY(d.alloc(&dX, nX));
+    ACE_TRY(d.alloc(&dY, nY));
+    ACE_TRY(d.alloc(&dW, ws));
+    ACE_TRY(d.alloc(&dI, (size_t)batch));
+    ACE_TRY(d.alloc(&dS, (size_t)batch));
+    ACE_TRY(d.alloc(&dM, (size_t)batch));
     ace_admm_cfg dcfg = *cfg;   // the per-realisation flags, if any, as a device array
     if (cfg->rank_one) {
-        ACE_HIPC(hipMemcpy(dR, cfg->rank_one, (size_t)batch, hipMemcpyHostToDevice));
-        dcfg.rank_one = (const uint8_t*)dR;
+        uint8_t* dR;
+        ACE_TRY(d.put(&dR, cfg->rank_one, (size_t)batch));
+        dcfg.rank_one = dR;
     }
-    rc = ace_admm_solve_batch(&dcfg, batch, m, n, tx, rx, (const double*)dA, (const double*)dB, (const double*)dX0,
-                              (double*)dX, (double*)dY, (int32_t*)dI, (uint32_t*)dS, (double*)dM, dW, ws, nullptr);
-    if (rc) {
-        std::string keep = g_err;
-        cleanup();
-        g_err = keep;
-        return rc;
-    }
-    ACE_HIPC(hipDeviceSynchronize());
-    ACE_HIPC(hipMemcpy(X, dX, nX, hipMemcpyDeviceToHost));
-    ACE_HIPC(hipMemcpy(Y, dY, nY, hipMemcpyDeviceToHost));
-    if (iters) ACE_HIPC(hipMemcpy(iters, dI, 4 * (size_t)batch, hipMemcpyDeviceToHost));
-    if (status) ACE_HIPC(hipMemcpy(status, dS, 4 * (size_t)batch, hipMemcpyDeviceToHost));
-    if (mu) ACE_HIPC(hipMemcpy(mu, dM, 8 * (size_t)batch, hipMemcpyDeviceToHost));
-#undef ACE_HIPC
-    cleanup();
-    return ACE_OK;
+    ACE_TRY(ace_admm_solve_batch(&dcfg, batch, m, n, tx, rx, dA, dB, dX0, dX, dY, dI, dS, dM, dW, ws, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(d.get(X, dX, nX));
+    ACE_TRY(d.get(Y, dY, nY));
+    ACE_TRY(d.get(iters, dI, (size_t)batch));
+    ACE_TRY(d.get(status, dS, (size_t)batch));
+    return d.get(mu, dM, (size_t)batch);
 }
 
 int ace_nuclear_prox_batch(int batch, int n, int r, const double* E, double tau, double* Z, void* stream) {

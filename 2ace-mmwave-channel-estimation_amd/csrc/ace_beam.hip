@@ -208,46 +208,28 @@ extern "C" int ace_svd_beamformer_host(int batch, int tx, int rx, const double* 
         return ace_svd_beamformer_batch(batch, tx, rx, H, offset, wr_code, wt_code, beam_idx, rss, status, vh_r,
                                         vh_t, nullptr);
     if (batch == 0) return ACE_OK;
-    const size_t B = batch, N = std::max(tx, rx), nH = 16 * B * tx * rx, nvr = 16 * B * rx * rx,
-                 nvt = 16 * B * tx * tx, noff = 8 * B * N, ncr = B * rx, nct = B * tx;
-    std::vector<void*> bufs;
-    auto cleanup = [&]() {
-        for (void* q : bufs) (void)hipFree(q);
-        bufs.clear();
-    };
-    auto dalloc = [&](size_t bytes, void** q) -> hipError_t {
-        hipError_t e = hipMalloc(q, bytes);
-        if (e == hipSuccess) bufs.push_back(*q);
-        return e;
-    };
-    void *dH, *doff = nullptr, *dwr, *dwt, *didx, *drss, *dst, *dvr = nullptr, *dvt = nullptr;
-    hipError_t e;
-    if ((e = dalloc(nH, &dH)) || (offset && (e = dalloc(noff, &doff))) || (e = dalloc(ncr, &dwr)) ||
-        (e = dalloc(nct, &dwt)) || (e = dalloc(8 * B, &didx)) || (e = dalloc(8 * B, &drss)) ||
-        (e = dalloc(4 * B, &dst)) || (vh_r && (e = dalloc(nvr, &dvr))) || (vh_t && (e = dalloc(nvt, &dvt)))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-    }
-    if ((e = hipMemcpy(dH, H, nH, hipMemcpyHostToDevice)) ||
-        (offset && (e = hipMemcpy(doff, offset, noff, hipMemcpyHostToDevice)))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    }
-    int rc = ace_svd_beamformer_batch(batch, tx, rx, (const double*)dH, (const double*)doff, (uint8_t*)dwr,
-                                      (uint8_t*)dwt, (int32_t*)didx, (double*)drss, (uint32_t*)dst, (double*)dvr,
-                                      (double*)dvt, nullptr);
-    if (rc == ACE_OK) {
-        if ((e = hipDeviceSynchronize()) || (e = hipMemcpy(wr_code, dwr, ncr, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(wt_code, dwt, nct, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(beam_idx, didx, 8 * B, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(rss, drss, 8 * B, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(status, dst, 4 * B, hipMemcpyDeviceToHost)) ||
-            (vh_r && (e = hipMemcpy(vh_r, dvr, nvr, hipMemcpyDeviceToHost))) ||
-            (vh_t && (e = hipMemcpy(vh_t, dvt, nvt, hipMemcpyDeviceToHost))))
-            rc = fail(ACE_ERR_HIP, "svd_beamformer: %s", hipGetErrorString(e));
-    }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    return rc;
+    const size_t B = batch, N = std::max(tx, rx), nvr = 2 * B * rx * rx, nvt = 2 * B * tx * tx;   // doubles
+    DevScope d;
+    double *dH, *doff = nullptr, *drss, *dvr = nullptr, *dvt = nullptr;
+    uint8_t *dwr, *dwt;
+    int32_t* didx;
+    uint32_t* dst;
+    ACE_TRY(d.put(&dH, H, 2 * B * tx * rx));
+    if (offset) ACE_TRY(d.put(&doff, offset, B * N));
+    ACE_TRY(d.alloc(&dwr, B * rx));
+    ACE_TRY(d.alloc(&dwt, B * tx));
+    ACE_TRY(d.alloc(&didx, 2 * B));
+    ACE_TRY(d.alloc(&drss, B));
+    ACE_TRY(d.alloc(&dst, B));
+    if (vh_r) ACE_TRY(d.alloc(&dvr, nvr));
+    if (vh_t) ACE_TRY(d.alloc(&dvt, nvt));
+    ACE_TRY(ace_svd_beamformer_batch(batch, tx, rx, dH, doff, dwr, dwt, didx, drss, dst, dvr, dvt, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(d.get(wr_code, dwr, B * rx));
+    ACE_TRY(d.get(wt_code, dwt, B * tx));
+    ACE_TRY(d.get(beam_idx, didx, 2 * B));
+    ACE_TRY(d.get(rss, drss, B));
+    ACE_TRY(d.get(status, dst, B));
+    ACE_TRY(d.get(vh_r, dvr, nvr));
+    return d.get(vh_t, dvt, nvt);
 }

@@ -102,24 +102,6 @@ inline double snap_unit(double v) {
     return v;
 }
 
-// A resident device buffer set for one sweep point, released on every exit path.
-struct DevBufs {
-    std::vector<void*> p;
-    hipStream_t st = nullptr;
-    hipError_t alloc(size_t bytes, void** q) {
-        hipError_t e = hipMalloc(q, bytes);
-        if (e == hipSuccess) p.push_back(*q);
-        return e;
-    }
-    ~DevBufs() {
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-        for (void* q : p) (void)hipFree(q);
-    }
-};
-
 // One sweep point i (M rows): rows, cb_train / rss_train, the solve, H row (:137-178).
 int sweep_point(int driver, int tx, int rx, int P, const double* cb_amp, const double* cb_angle,
                 const double* rss_dbm, uint64_t seed, int i, int M, int dev, int maxiter, double* H_amp,
@@ -161,10 +143,11 @@ int sweep_point(int driver, int tx, int rx, int P, const double* cb_amp, const d
             return ACE_OK;
         }
     }
-    DevBufs d;
-    ACE_HIP(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking));
-    void *dA, *dB, *dX, *dY, *dW;
-    const size_t nA = 16 * (size_t)M * n, nB = 8 * (size_t)M, nX = 16 * (size_t)n, nY = 16 * (size_t)M;
+    DevScope d;   // this point's device buffers and stream, released on every exit path
+    ACE_TRY(d.own_stream());
+    double *dA, *dB, *dX, *dY;
+    char* dW;
+    const size_t nA = 2 * (size_t)M * n, nX = 2 * (size_t)n;   // doubles
     if (driver == ACE_DRIVER_PHASELIFT) {
         // ---- Recover_Channel.m:32-35: MyPhaseLift((meas/2e5).^2*1e10, beams)/sqrt(1e10)*2e5
         ace_phaselift_cfg pcfg;
@@ -173,15 +156,12 @@ int sweep_point(int driver, int tx, int rx, int P, const double* cb_amp, const d
         for (int r = 0; r < M; ++r) B[r] = (B[r] / 2e5) * (B[r] / 2e5) * 1e10;
         const size_t ws = ace_phaselift_workspace_size(&pcfg, 1, M, n);
         if (!ws) return fail(ACE_ERR_UNSUPPORTED, "phaselift: unsupported size M = %d, n = %d", M, n);
-        ACE_HIP(d.alloc(nA, &dA));
-        ACE_HIP(d.alloc(nB, &dB));
-        ACE_HIP(d.alloc(nX, &dX));
-        ACE_HIP(d.alloc(ws, &dW));
-        ACE_HIP(upload(dA, A.data(), nA, d.st));
-        ACE_HIP(upload(dB, B.data(), nB, d.st));
-        ACE_TRY(ace_phaselift_solve_batch(&pcfg, 1, M, n, (const double*)dA, (const double*)dB, (double*)dX, nullptr,
-                                          nullptr, dW, ws, d.st));
-        ACE_HIP(read_back(X.data(), dX, nX, d.st));
+        ACE_TRY(d.put(&dA, A.data(), nA));
+        ACE_TRY(d.put(&dB, B.data(), (size_t)M));
+        ACE_TRY(d.alloc(&dX, nX));
+        ACE_TRY(d.alloc(&dW, ws));
+        ACE_TRY(ace_phaselift_solve_batch(&pcfg, 1, M, n, dA, dB, dX, nullptr, nullptr, dW, ws, d.st));
+        ACE_TRY(d.get(X.data(), dX, nX));
         for (int k = 0; k < 2 * n; ++k) X[k] = X[k] / std::sqrt(1e10) * 2e5;
     } else {
         // ---- Recover_Channel -> ADMM_v2(..., 4): the pipeline with its own train partitions
@@ -191,16 +171,14 @@ int sweep_point(int driver, int tx, int rx, int P, const double* cb_amp, const d
             randperm_k(seed, 0x101 + 2 * (uint64_t)i + 0x10000 * (uint64_t)s, M, mt, tr.data() + (size_t)s * mt);
         const size_t ws = ace_pipeline_workspace_size(&cfg, 1, M, n);
         if (!ws) return fail(ACE_ERR_UNSUPPORTED, "pipeline: unsupported size M = %d, n = %d", M, n);
-        ACE_HIP(d.alloc(nA, &dA));
-        ACE_HIP(d.alloc(nB, &dB));
-        ACE_HIP(d.alloc(nX, &dX));
-        ACE_HIP(d.alloc(nY, &dY));
-        ACE_HIP(d.alloc(ws, &dW));
-        ACE_HIP(upload(dA, A.data(), nA, d.st));
-        ACE_HIP(upload(dB, B.data(), nB, d.st));
-        ACE_TRY(ace_pipeline_solve_batch(&cfg, 1, M, n, tx, rx, (const double*)dA, (const double*)dB, tr.data(),
-                                         (double*)dX, (double*)dY, nullptr, nullptr, nullptr, dW, ws, d.st));
-        ACE_HIP(read_back(X.data(), dX, nX, d.st));
+        ACE_TRY(d.put(&dA, A.data(), nA));
+        ACE_TRY(d.put(&dB, B.data(), (size_t)M));
+        ACE_TRY(d.alloc(&dX, nX));
+        ACE_TRY(d.alloc(&dY, 2 * (size_t)M));
+        ACE_TRY(d.alloc(&dW, ws));
+        ACE_TRY(ace_pipeline_solve_batch(&cfg, 1, M, n, tx, rx, dA, dB, tr.data(), dX, dY, nullptr, nullptr, nullptr, dW,
+                                         ws, d.st));
+        ACE_TRY(d.get(X.data(), dX, nX));
     }
     // ---- :170-178 H_out = X / rss_fct, NaN -> 0, amplitude and angle
     for (int k = 0; k < n; ++k) {

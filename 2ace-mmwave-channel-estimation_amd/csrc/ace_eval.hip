@@ -229,29 +229,16 @@ extern "C" int ace_evaluate_host(int batch, int tx, int rx, const double* X, con
                                  uint32_t* status) {
     g_err.clear();
     ACE_TRY(ev_check_args(batch, tx, rx, X, G, metrics));
-    const size_t B = batch, nv = 16 * B * tx * rx;
-    void* buf[4] = {nullptr, nullptr, nullptr, nullptr};   // X, G, metrics, status
-    const size_t bytes[4] = {nv, nv, 32 * B, 4 * B};
-    auto cleanup = [&]() {
-        for (void* q : buf)
-            if (q) (void)hipFree(q);
-    };
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipMalloc(&buf[i], bytes[i]);
-    if (e == hipSuccess) e = hipMemcpy(buf[0], X, nv, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf[1], G, nv, hipMemcpyHostToDevice);
-    int rc = ACE_OK;
-    if (e == hipSuccess)
-        rc = ace_evaluate_batch(batch, tx, rx, (const double*)buf[0], (const double*)buf[1], (double*)buf[2],
-                                (uint32_t*)buf[3], nullptr);
-    if (e == hipSuccess && rc == ACE_OK) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(metrics, buf[2], bytes[2], hipMemcpyDeviceToHost);
-        if (e == hipSuccess && status) e = hipMemcpy(status, buf[3], bytes[3], hipMemcpyDeviceToHost);
-    }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    if (e != hipSuccess) return fail(ACE_ERR_HIP, "evaluate: %s", hipGetErrorString(e));
-    return rc;
+    const size_t B = batch, nv = 2 * B * tx * rx;   // doubles
+    DevScope d;
+    double *dX, *dG, *dmet;
+    uint32_t* dst;
+    ACE_TRY(d.put(&dX, X, nv));
+    ACE_TRY(d.put(&dG, G, nv));
+    ACE_TRY(d.alloc(&dmet, 4 * B));
+    ACE_TRY(d.alloc(&dst, B));
+    ACE_TRY(ace_evaluate_batch(batch, tx, rx, dX, dG, dmet, dst, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(d.get(metrics, dmet, 4 * B));
+    return d.get(status, dst, B);
 }

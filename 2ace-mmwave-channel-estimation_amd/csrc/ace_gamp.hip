@@ -773,30 +773,26 @@ extern "C" int ace_gamp_solve_host(const ace_gamp_cfg* cfg, int batch, int d, in
     g_err.clear();
     ACE_TRY(ga_check_args(cfg, batch, d, N, D, Y, xhat, params, em_iters));
     const size_t B = batch, wsb = ga_ws_bytes(batch, d, N), ntr = 2 * B * ((size_t)cfg->max_em_iter + 1);
-    // D, Y | xhat, xvar, params, em_iters, trace, status | workspace
-    void* buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[9] = {16 * (size_t)d * N, 16 * B * d, 16 * B * N, 8 * B * N, 24 * B, 4 * B, 4 * ntr, 4 * B, wsb};
-    const void* src[2] = {D, Y};
-    void* dst[8] = {nullptr, nullptr, xhat, xvar, params, em_iters, trace, status};
-    const bool use[9] = {true, true, true, xvar != nullptr, true, true, trace != nullptr, status != nullptr, true};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 9 && e == hipSuccess; ++i)
-        if (use[i]) e = hipMalloc(&buf[i], bytes[i]);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMemcpy(buf[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    int rc = ACE_OK;
-    if (e == hipSuccess)
-        rc = ace_gamp_solve_batch(cfg, batch, d, N, (const double*)buf[0], (const double*)buf[1], (double*)buf[2],
-                                  (double*)buf[3], (double*)buf[4], (int32_t*)buf[5], (int32_t*)buf[6], (uint32_t*)buf[7],
-                                  buf[8], wsb, nullptr);
-    if (e == hipSuccess && rc == ACE_OK) {
-        e = hipDeviceSynchronize();
-        for (int i = 2; i < 8 && e == hipSuccess; ++i)
-            if (use[i]) e = hipMemcpy(dst[i], buf[i], bytes[i], hipMemcpyDeviceToHost);
-    }
-    const std::string keep = g_err;
-    for (void* q : buf)
-        if (q) (void)hipFree(q);
-    g_err = keep;
-    if (e != hipSuccess) return fail(ACE_ERR_HIP, "gamp: %s", hipGetErrorString(e));
-    return rc;
+    DevScope dev;
+    double *dD, *dY, *dxhat, *dxvar = nullptr, *dpar;
+    int32_t *dem, *dtr = nullptr;
+    uint32_t* dst = nullptr;
+    char* dws;
+    ACE_TRY(dev.put(&dD, D, 2 * (size_t)d * N));
+    ACE_TRY(dev.put(&dY, Y, 2 * B * d));
+    ACE_TRY(dev.alloc(&dxhat, 2 * B * N));
+    if (xvar) ACE_TRY(dev.alloc(&dxvar, B * N));
+    ACE_TRY(dev.alloc(&dpar, 3 * B));
+    ACE_TRY(dev.alloc(&dem, B));
+    if (trace) ACE_TRY(dev.alloc(&dtr, ntr));
+    if (status) ACE_TRY(dev.alloc(&dst, B));
+    ACE_TRY(dev.alloc(&dws, wsb));
+    ACE_TRY(ace_gamp_solve_batch(cfg, batch, d, N, dD, dY, dxhat, dxvar, dpar, dem, dtr, dst, dws, wsb, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(dev.get(xhat, dxhat, 2 * B * N));
+    ACE_TRY(dev.get(xvar, dxvar, B * N));
+    ACE_TRY(dev.get(params, dpar, 3 * B));
+    ACE_TRY(dev.get(em_iters, dem, B));
+    ACE_TRY(dev.get(trace, dtr, ntr));
+    return dev.get(status, dst, B);
 }

@@ -1,6 +1,7 @@
 // Host-side helpers shared by the C-ABI translation units (ace_api.cpp, ace_admm.cpp,
 // ace_pipeline.cpp): thread-local error text, HIP error checks, the event-pair kernel
-// timer behind ace_prof_start/stop, and the ArgMinZ rank profile.
+// timer behind ace_prof_start/stop, the ArgMinZ rank profile, and the device buffers of the
+// host-array entries (DevScope).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,6 +171,83 @@ struct Carver {
         return reinterpret_cast<T*>(p);
     }
 };
+
+// The device allocations of one host-array call (hipMalloc, never the stream-ordered pool: DESIGN.md
+// §9 item 7), freed on every exit path.  With a stream (own_stream / borrow) the destructor drains it before
+// the frees.  Copies are hipMemcpy on the null stream, or, with an owned stream, the pinned-staging
+// upload / read_back on it.  Failures come back as ACE_ERR_HIP with the error text set.
+template <class T>
+struct NoDeduce {
+    using type = T;
+};
+struct DevScope {
+    std::vector<void*> bufs;
+    hipStream_t st = nullptr;
+    bool drain = false, owned = false;
+    DevScope() = default;
+    DevScope(const DevScope&) = delete;
+    DevScope& operator=(const DevScope&) = delete;
+    ~DevScope() {
+        if (drain) (void)hipStreamSynchronize(st);
+        if (owned) (void)hipStreamDestroy(st);
+        for (void* p : bufs) (void)hipFree(p);
+    }
+    int own_stream() {   // a non-blocking stream of this call's own
+        ACE_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        drain = owned = true;
+        return ACE_OK;
+    }
+    void borrow(hipStream_t s) {   // the caller's stream: the work on it must finish before the buffers go
+        st = s;
+        drain = true;
+    }
+    template <class T>
+    int alloc(T** p, size_t count) {   // (at least one element is allocated)
+        void* q = nullptr;
+        ACE_HIP(hipMalloc(&q, sizeof(T) * (count ? count : 1)));
+        bufs.push_back(q);
+        *p = static_cast<T*>(q);
+        return ACE_OK;
+    }
+    // dst[0 .. count) = src, or `fill` where src is null
+    template <class T>
+    int set(T* dst, const typename NoDeduce<T>::type* src, size_t count, typename NoDeduce<T>::type fill = T{}) {
+        if (!count) return ACE_OK;
+        std::vector<T> tmp;
+        if (!src) {
+            tmp.assign(count, fill);
+            src = tmp.data();
+        }
+        if (owned) ACE_HIP(upload(dst, src, sizeof(T) * count, st));
+        else ACE_HIP(hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
+        return ACE_OK;
+    }
+    template <class T>
+    int put(T** p, const typename NoDeduce<T>::type* src, size_t count, typename NoDeduce<T>::type fill = T{}) {
+        ACE_TRY(alloc(p, count));
+        return set(*p, src, count, fill);
+    }
+    template <class T>
+    int get(T* dst, const typename NoDeduce<T>::type* src, size_t count) {   // dst may be null
+        if (!dst || !count) return ACE_OK;
+        if (owned) ACE_HIP(read_back(dst, src, sizeof(T) * count, st));
+        else ACE_HIP(hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
+        return ACE_OK;
+    }
+};
+
+// One zeroed allocation of `d` laid out by carve(Carver&), which runs twice: to measure, then on the buffer.
+template <class F>
+int carve_zeroed(DevScope& d, F&& carve) {
+    Carver measure{nullptr};
+    carve(measure);
+    char* ws;
+    ACE_TRY(d.alloc(&ws, measure.off));
+    ACE_HIP(hipMemset(ws, 0, measure.off));
+    Carver cv{ws};
+    carve(cv);
+    return ACE_OK;
+}
 
 // ---- one ADMM solve (InferADMM, inferLowRankV4_multi.m:281-386) over a batch -------
 // The sensing operator of the solve.  Shared regime: one A (m x n) for the batch with

@@ -12,30 +12,6 @@
 namespace ace {
 namespace {
 
-struct DevBuf {   // one device allocation, freed on scope exit
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-int h2d(void* dst, const void* src, size_t bytes) {
-    if (!bytes) return ACE_OK;
-    ACE_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return ACE_OK;
-}
-int d2h(void* dst, const void* src, size_t bytes) {
-    if (!bytes) return ACE_OK;
-    ACE_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return ACE_OK;
-}
-// device buffer of `count` doubles holding src, or `fill` where src is null
-int put(double* dst, const double* src, size_t count, double fill, std::vector<double>& tmp) {
-    if (src) return h2d(dst, src, 8 * count);
-    tmp.assign(count, fill);
-    return h2d(dst, tmp.data(), 8 * count);
-}
-
 int linop_run(const ace_linop_args& a) {
     const int m = a.m, n = a.n, batch = a.batch, r = a.rcols, op = a.op, path = a.path;
     const bool shared = a.a_shared != 0, i8 = path == ACE_LINOP_I8;
@@ -80,16 +56,11 @@ int linop_run(const ace_linop_args& a) {
         dzeros = cv.take(16 * (size_t)n);
         drs = cv.take<RealState>(sizeof(RealState) * (size_t)batch);
     };
-    Carver measure{nullptr};
-    carve(measure);
-    DevBuf ws;
-    ACE_HIP(hipMalloc(&ws.p, measure.off));
-    ACE_HIP(hipMemset(ws.p, 0, measure.off));
-    Carver cv{static_cast<char*>(ws.p)};
-    carve(cv);
+    DevScope d;
+    ACE_TRY(carve_zeroed(d, carve));
     hipStream_t st = nullptr;
 
-    ACE_TRY(h2d(dA, a.A, 16 * (size_t)mats * mn));
+    ACE_TRY(d.set(dA, a.A, 2 * (size_t)mats * mn));
     L.A = dA;
     L.allow_i8 = i8;
     ACE_TRY(linops_setup(L, batch, st));
@@ -99,11 +70,11 @@ int linop_run(const ace_linop_args& a) {
 
     if (op == ACE_LINOP_SETUP) {
         ACE_HIP(hipDeviceSynchronize());
-        ACE_TRY(d2h(a.out, L.K, 16 * (size_t)mats * mm));
-        ACE_TRY(d2h(a.out2, L.G, 16 * (size_t)mats * mm));
+        ACE_TRY(d.get(a.out, L.K, 2 * (size_t)mats * mm));
+        ACE_TRY(d.get(a.out2, L.G, 2 * (size_t)mats * mm));
         if (a.out3) {
             double c[2] = {0.0, 0.0};
-            if (i8) ACE_TRY(d2h(c, L.c8, sizeof c));
+            if (i8) ACE_TRY(d.get(c, L.c8, 2));
             a.out3[0] = c[0];
             a.out3[1] = c[1];
         }
@@ -119,23 +90,22 @@ int linop_run(const ace_linop_args& a) {
         rs[b].nzero = a.nzero ? a.nzero[b] : 0;
         rs[b].avok = a.avok ? a.avok[b] : 0;
     }
-    ACE_TRY(h2d(drs, rs.data(), sizeof(RealState) * rs.size()));
-    std::vector<double> tmp;
+    ACE_TRY(d.set(drs, rs.data(), rs.size()));
     if (needZ) {
-        ACE_TRY(h2d(dZ, a.Z, 8 * bn));
-        ACE_TRY(put(dN, a.N, bn, 0.0, tmp));
+        ACE_TRY(d.set(dZ, a.Z, bn));
+        ACE_TRY(d.set(dN, a.N, bn, 0.0));
     }
     if (needY) {
-        ACE_TRY(h2d(dY, a.Y, 8 * bm));
-        ACE_TRY(put(dM, a.M, bm, 0.0, tmp));
+        ACE_TRY(d.set(dY, a.Y, bm));
+        ACE_TRY(d.set(dM, a.M, bm, 0.0));
     }
-    if (needg) ACE_TRY(h2d(dg, a.g, 8 * bm));
-    if (a.AX) ACE_TRY(h2d(dAX, a.AX, 8 * bm));
+    if (needg) ACE_TRY(d.set(dg, a.g, bm));
+    if (a.AX) ACE_TRY(d.set(dAX, a.AX, bm));
     const size_t nout = (op == ACE_LINOP_AH) ? bn : bm;
-    ACE_TRY(put(dout, nullptr, nout, a.sentinel, tmp));
+    ACE_TRY(d.set(dout, nullptr, nout, a.sentinel));
     // the intermediates a launch_pre writes start from the sentinel too (a row it skips stays visible)
-    ACE_TRY(put(dV, nullptr, bn, a.sentinel, tmp));
-    ACE_TRY(put(dS, nullptr, bm, a.sentinel, tmp));
+    ACE_TRY(d.set(dV, nullptr, bn, a.sentinel));
+    ACE_TRY(d.set(dS, nullptr, bm, a.sentinel));
 
     switch (op) {
     case ACE_LINOP_A:   // T = (Y - M/mu) - A (Z - N/mu)
@@ -181,7 +151,7 @@ int linop_run(const ace_linop_args& a) {
     }
     ACE_LAUNCHED("ace_linop_host");
     ACE_HIP(hipDeviceSynchronize());
-    ACE_TRY(d2h(a.out, dout, 8 * nout));
+    ACE_TRY(d.get(a.out, dout, nout));
     return ACE_OK;
 }
 
@@ -210,26 +180,18 @@ int ace_zgemm_host(int mode, int conj_l, int M, int K, int nb, const double* L, 
     if (z1 * strideL + (long long)(M - 1) * ldl + K > nL || z1 * strideV + (long long)(nb - 1) * ldv + K > nV ||
         z1 * strideC + (long long)(nb - 1) * ldc + M > nC || (klim && z1 * klim_stride + 1 > nklim))
         return fail(ACE_ERR_ARG, "ace_zgemm_host: operand extents exceed the given array sizes");
-    DevBuf dL, dV, dC, dE, dk;
-    ACE_HIP(hipMalloc(&dL.p, 16 * (size_t)nL));
-    ACE_HIP(hipMalloc(&dV.p, 16 * (size_t)nV));
-    ACE_HIP(hipMalloc(&dC.p, 16 * (size_t)nC));
-    ACE_TRY(h2d(dL.p, L, 16 * (size_t)nL));
-    ACE_TRY(h2d(dV.p, V, 16 * (size_t)nV));
-    ACE_TRY(h2d(dC.p, C, 16 * (size_t)nC));
-    if (mode != 0) {
-        ACE_HIP(hipMalloc(&dE.p, 16 * (size_t)nC));
-        ACE_TRY(h2d(dE.p, E, 16 * (size_t)nC));
-    }
-    if (klim) {
-        ACE_HIP(hipMalloc(&dk.p, 8 * (size_t)nklim));
-        ACE_TRY(h2d(dk.p, klim, 8 * (size_t)nklim));
-    }
-    launch_zgemm(mode, conj_l != 0, M, K, nb, (const double*)dL.p, ldl, strideL, (const double*)dV.p, ldv, strideV,
-                 (double*)dC.p, (const double*)dE.p, ldc, strideC, nz, nullptr, (const double*)dk.p, klim_stride);
+    DevScope d;
+    double *dL, *dV, *dC, *dE = nullptr, *dk = nullptr;
+    ACE_TRY(d.put(&dL, L, 2 * (size_t)nL));
+    ACE_TRY(d.put(&dV, V, 2 * (size_t)nV));
+    ACE_TRY(d.put(&dC, C, 2 * (size_t)nC));
+    if (mode != 0) ACE_TRY(d.put(&dE, E, 2 * (size_t)nC));
+    if (klim) ACE_TRY(d.put(&dk, klim, (size_t)nklim));
+    launch_zgemm(mode, conj_l != 0, M, K, nb, dL, ldl, strideL, dV, ldv, strideV, dC, dE, ldc, strideC, nz, nullptr, dk,
+                 klim_stride);
     ACE_LAUNCHED("ace_zgemm_host");
     ACE_HIP(hipDeviceSynchronize());
-    ACE_TRY(d2h(C, dC.p, 16 * (size_t)nC));
+    ACE_TRY(d.get(C, dC, 2 * (size_t)nC));
     return ACE_OK;
 }
 

@@ -406,32 +406,27 @@ extern "C" int ace_omp_solve_host(int batch, int d, int N, int kmax, double tol,
     g_err.clear();
     ACE_TRY(om_check_args(batch, d, N, kmax, tol, D, Y, idx, coef, count, resnorm));
     const size_t B = batch, wsb = om_ws_bytes(batch, d, kmax);
-    // D, colscale, Y | idx, coef, count, resnorm, status, x | workspace
-    void* buf[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[10] = {16 * (size_t)d * N, 8 * (size_t)N, 16 * B * d, 4 * B * kmax, 16 * B * kmax,
-                              4 * B,              8 * B,         4 * B,      16 * B * N,   wsb};
-    const void* src[3] = {D, colscale, Y};
-    void* dst[9] = {nullptr, nullptr, nullptr, idx, coef, count, resnorm, status, x};
-    const bool use[10] = {true, colscale != nullptr, true, true, true, true, true, true, x != nullptr, true};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 10 && e == hipSuccess; ++i)
-        if (use[i]) e = hipMalloc(&buf[i], bytes[i]);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i)
-        if (use[i]) e = hipMemcpy(buf[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    int rc = ACE_OK;
-    if (e == hipSuccess)
-        rc = ace_omp_solve_batch(batch, d, N, kmax, tol, (const double*)buf[0], (const double*)buf[1], (const double*)buf[2],
-                                 (int32_t*)buf[3], (double*)buf[4], (int32_t*)buf[5], (double*)buf[6], (uint32_t*)buf[7],
-                                 (double*)buf[8], buf[9], wsb, nullptr);
-    if (e == hipSuccess && rc == ACE_OK) {
-        e = hipDeviceSynchronize();
-        for (int i = 3; i < 9 && e == hipSuccess; ++i)
-            if (use[i] && dst[i]) e = hipMemcpy(dst[i], buf[i], bytes[i], hipMemcpyDeviceToHost);
-    }
-    const std::string keep = g_err;
-    for (void* q : buf)
-        if (q) (void)hipFree(q);
-    g_err = keep;
-    if (e != hipSuccess) return fail(ACE_ERR_HIP, "omp: %s", hipGetErrorString(e));
-    return rc;
+    DevScope dev;
+    double *dD, *dcs = nullptr, *dY, *dcoef, *dres, *dx = nullptr;
+    int32_t *didx, *dcount;
+    uint32_t* dst;
+    char* dws;
+    ACE_TRY(dev.put(&dD, D, 2 * (size_t)d * N));
+    if (colscale) ACE_TRY(dev.put(&dcs, colscale, (size_t)N));
+    ACE_TRY(dev.put(&dY, Y, 2 * B * d));
+    ACE_TRY(dev.alloc(&didx, B * kmax));
+    ACE_TRY(dev.alloc(&dcoef, 2 * B * kmax));
+    ACE_TRY(dev.alloc(&dcount, B));
+    ACE_TRY(dev.alloc(&dres, B));
+    ACE_TRY(dev.alloc(&dst, B));
+    if (x) ACE_TRY(dev.alloc(&dx, 2 * B * N));
+    ACE_TRY(dev.alloc(&dws, wsb));
+    ACE_TRY(ace_omp_solve_batch(batch, d, N, kmax, tol, dD, dcs, dY, didx, dcoef, dcount, dres, dst, dx, dws, wsb, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(dev.get(idx, didx, B * kmax));
+    ACE_TRY(dev.get(coef, dcoef, 2 * B * kmax));
+    ACE_TRY(dev.get(count, dcount, B));
+    ACE_TRY(dev.get(resnorm, dres, B));
+    ACE_TRY(dev.get(status, dst, B));
+    return dev.get(x, dx, 2 * B * N);
 }

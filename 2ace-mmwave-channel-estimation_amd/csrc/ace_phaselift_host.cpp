@@ -242,42 +242,26 @@ int solve_host(const ace_phaselift_cfg* cfg, int batch, int m, int n, const doub
     g_err.clear();
     PlDims D;
     ACE_TRY(validate(cfg, batch, m, n, &D));
-    const size_t nP = 16 * (size_t)m * n, nb = 8 * (size_t)batch * m, ns = 16 * (size_t)batch * n,
-                 nx = 16 * (size_t)batch * D.d * D.d, ws = ace_phaselift_workspace_size(cfg, batch, m, n);
-    std::vector<void*> bufs;
-    auto cleanup = [&]() {
-        for (void* q : bufs) (void)hipFree(q);
-        bufs.clear();
-    };
-    auto dalloc = [&](size_t bytes, void** q) -> hipError_t {
-        hipError_t e = hipMalloc(q, bytes);
-        if (e == hipSuccess) bufs.push_back(*q);
-        return e;
-    };
-    void *dP, *db, *ds, *di, *dst, *dw, *dx = nullptr;
-    hipError_t e;
-    if ((e = dalloc(nP, &dP)) || (e = dalloc(nb, &db)) || (e = dalloc(ns, &ds)) || (e = dalloc(4 * (size_t)batch, &di)) ||
-        (e = dalloc(4 * (size_t)batch, &dst)) || (e = dalloc(ws, &dw)) || (Xr && (e = dalloc(nx, &dx)))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-    }
-    if ((e = hipMemcpy(dP, Phi, nP, hipMemcpyHostToDevice)) || (e = hipMemcpy(db, bvec, nb, hipMemcpyHostToDevice))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    }
-    int rc = solve_batch(cfg, batch, m, n, (const double*)dP, (const double*)db, (double*)ds, (int32_t*)di,
-                         (uint32_t*)dst, dw, ws, nullptr, (double*)dx);
-    if (rc == ACE_OK) {
-        if ((e = hipDeviceSynchronize()) || (e = hipMemcpy(sig, ds, ns, hipMemcpyDeviceToHost)) ||
-            (iters && (e = hipMemcpy(iters, di, 4 * (size_t)batch, hipMemcpyDeviceToHost))) ||
-            (status && (e = hipMemcpy(status, dst, 4 * (size_t)batch, hipMemcpyDeviceToHost))) ||
-            (Xr && (e = hipMemcpy(Xr, dx, nx, hipMemcpyDeviceToHost))))
-            rc = fail(ACE_ERR_HIP, "phaselift: %s", hipGetErrorString(e));
-    }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    return rc;
+    const size_t ns = 2 * (size_t)batch * n, nx = 2 * (size_t)batch * D.d * D.d,   // doubles
+                 ws = ace_phaselift_workspace_size(cfg, batch, m, n);
+    DevScope dev;
+    double *dP, *db, *ds, *dx = nullptr;
+    int32_t* di;
+    uint32_t* dst;
+    char* dw;
+    ACE_TRY(dev.put(&dP, Phi, 2 * (size_t)m * n));
+    ACE_TRY(dev.put(&db, bvec, (size_t)batch * m));
+    ACE_TRY(dev.alloc(&ds, ns));
+    ACE_TRY(dev.alloc(&di, (size_t)batch));
+    ACE_TRY(dev.alloc(&dst, (size_t)batch));
+    ACE_TRY(dev.alloc(&dw, ws));
+    if (Xr) ACE_TRY(dev.alloc(&dx, nx));
+    ACE_TRY(solve_batch(cfg, batch, m, n, dP, db, ds, di, dst, dw, ws, nullptr, dx));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(dev.get(sig, ds, ns));
+    ACE_TRY(dev.get(iters, di, (size_t)batch));
+    ACE_TRY(dev.get(status, dst, (size_t)batch));
+    return dev.get(Xr, dx, nx);
 }
 }  // namespace
 
@@ -309,38 +293,24 @@ int ace_prox_eig_host(int batch, int d, int path, const double* A, const double*
     g_err.clear();
     if (batch < 1 || d < 2 || d > 1600 || !A || !tau || !lam || !V || !k) return fail(ACE_ERR_ARG, "bad ace_prox_eig_host arguments");
     const HeevLayout hl = heev_layout(d, d);
-    const size_t dd = 16 * (size_t)d * d, sb = heev_scratch_bytes(d, d, batch);
-    void *ds = nullptr, *dt = nullptr, *dv = nullptr;
-    auto cleanup = [&]() {
-        for (void* q : {ds, dt, dv}) (void)hipFree(q);
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&ds, sb)) || (e = hipMalloc(&dt, 8 * (size_t)batch)) || (e = hipMalloc(&dv, dd * batch))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-    }
-    double* sc = (double*)ds;
-    int rc = ACE_OK;
-    for (int b = 0; b < batch && !rc; ++b)
-        if ((e = hipMemcpy(sc + (size_t)b * hl.stride + hl.C, A + 2 * (size_t)b * d * d, dd, hipMemcpyHostToDevice)))
-            rc = fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    if (!rc && (e = hipMemcpy(dt, tau, 8 * (size_t)batch, hipMemcpyHostToDevice)))
-        rc = fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_heev(d, d, batch, (const double*)dt, sc, (double*)dv, nullptr, nullptr, nullptr, path & 3, path >> 2);
-    if (!rc) rc = launch_check("prox eig", __FILE__, __LINE__);
-    if (!rc && (e = hipDeviceSynchronize())) rc = fail(ACE_ERR_HIP, "prox eig: %s", hipGetErrorString(e));
-    if (!rc && (e = hipMemcpy(V, dv, dd * batch, hipMemcpyDeviceToHost))) rc = fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    for (int b = 0; b < batch && !rc; ++b) {
+    const size_t dd = 2 * (size_t)d * d, sb = heev_scratch_bytes(d, d, batch);   // dd: doubles of one matrix
+    DevScope dev;
+    double *sc, *dt, *dv;
+    ACE_TRY(dev.alloc(&sc, (sb + 7) / 8));
+    ACE_TRY(dev.alloc(&dv, dd * batch));
+    for (int b = 0; b < batch; ++b) ACE_TRY(dev.set(sc + (size_t)b * hl.stride + hl.C, A + dd * b, dd));
+    ACE_TRY(dev.put(&dt, tau, (size_t)batch));
+    ACE_TRY(launch_heev(d, d, batch, dt, sc, dv, nullptr, nullptr, nullptr, path & 3, path >> 2));
+    ACE_LAUNCHED("prox eig");
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(dev.get(V, dv, dd * batch));
+    for (int b = 0; b < batch; ++b) {
         double misc[3] = {0.0, 0.0, 0.0};
-        if ((e = hipMemcpy(misc, sc + (size_t)b * hl.stride + hl.misc, 24, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(lam + (size_t)b * d, sc + (size_t)b * hl.stride + hl.lam, 8 * (size_t)d, hipMemcpyDeviceToHost)))
-            rc = fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
+        ACE_TRY(dev.get(misc, sc + (size_t)b * hl.stride + hl.misc, 3));
+        ACE_TRY(dev.get(lam + (size_t)b * d, sc + (size_t)b * hl.stride + hl.lam, (size_t)d));
         k[b] = misc[2] != 0.0 ? -(int32_t)misc[0] : (int32_t)misc[0];
     }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    return rc;
+    return ACE_OK;
 }
 
 }  // extern "C"

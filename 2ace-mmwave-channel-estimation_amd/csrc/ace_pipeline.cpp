@@ -407,35 +407,20 @@ int ace_spectral_init_host(int batch, int m, int n, int r, const double* A, cons
     if (r > 32 || r > m || r > n) return fail(ACE_ERR_UNSUPPORTED, "r must be <= min(32, m, n) (got %d)", r);
     if (std::min(m, n) > 1600) return fail(ACE_ERR_UNSUPPORTED, "min(m, n) = %d > 1600 (LDS limit)", std::min(m, n));
     const bool primal = spectral_primal(m, n);
-    const size_t nA = 16 * (size_t)m * n, nK = 16 * (size_t)m * m, nB = 8 * (size_t)batch * m,
-                 nW = 16 * (size_t)batch * r * m, nX = 16 * (size_t)batch * r * n,
-                 nS = spectral_scratch_bytes(m, n, batch, r);
-    std::vector<void*> bufs;
-    struct Free {
-        std::vector<void*>& b;
-        hipStream_t st = nullptr;
-        ~Free() {
-            if (st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-            for (void* p : b) (void)hipFree(p);
-        }
-    } guard{bufs};
-    auto dalloc = [&](size_t bytes) -> double* {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return static_cast<double*>(p);
-    };
-    double *dA = dalloc(nA), *dAH = dalloc(nA), *dK = dalloc(nK), *dB = dalloc(nB), *dW = dalloc(primal ? 16 : nW),
-           *dX = dalloc(nX), *dS = dalloc(nS);
-    int* dst = reinterpret_cast<int*>(dalloc(4 * (size_t)batch));
-    if (!dA || !dAH || !dK || !dB || !dW || !dX || !dS || !dst) return fail(ACE_ERR_HIP, "device allocation failed");
-    ACE_HIP(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
-    hipStream_t st = guard.st;
-    ACE_HIP(upload(dA, A, nA, st));
-    ACE_HIP(upload(dB, B, nB, st));
+    const size_t nA = 2 * (size_t)m * n, nX = 2 * (size_t)batch * r * n;   // doubles
+    DevScope d;
+    ACE_TRY(d.own_stream());
+    hipStream_t st = d.st;
+    double *dA, *dAH, *dK, *dB, *dW, *dX, *dS;
+    int* dst;
+    ACE_TRY(d.put(&dA, A, nA));
+    ACE_TRY(d.alloc(&dAH, nA));
+    ACE_TRY(d.alloc(&dK, 2 * (size_t)m * m));
+    ACE_TRY(d.put(&dB, B, (size_t)batch * m));
+    ACE_TRY(d.alloc(&dW, primal ? 2 : 2 * (size_t)batch * r * m));
+    ACE_TRY(d.alloc(&dX, nX));
+    ACE_TRY(d.alloc(&dS, (spectral_scratch_bytes(m, n, batch, r) + 7) / 8));
+    ACE_TRY(d.alloc(&dst, (size_t)batch));
     ACE_HIP(hipMemsetAsync(dst, 0, 4 * (size_t)batch, st));
     launch_conj_transpose(m, n, dA, dAH, st);
     launch_zgemm(0, true, m, n, m, dA, n, 0, dA, n, 0, dK, nullptr, m, 0, 1, st);   // K = A A^H
@@ -448,9 +433,8 @@ int ace_spectral_init_host(int batch, int m, int n, int r, const double* A, cons
         launch_zgemm(0, false, n, m, batch * r, dAH, m, 0, dW, m, 0, dX, nullptr, n, 0, 1, st);
     }
     ACE_LAUNCHED("nuclear spectral initialisation");
-    ACE_HIP(read_back(X, dX, nX, st));
-    if (status) ACE_HIP(read_back(status, dst, 4 * (size_t)batch, st));
-    return ACE_OK;
+    ACE_TRY(d.get(X, dX, nX));
+    return d.get(reinterpret_cast<int*>(status), dst, (size_t)batch);
 }
 
 
@@ -669,45 +653,28 @@ int ace_pipeline_solve_host(const ace_pipeline_cfg* cfg, int batch, int m, int n
     PipeDims d;
     ACE_TRY(validate(cfg, batch, m, n, tx, rx, &d));
     const int ld = 4 * d.restarts + 1;
-    const size_t nA = (size_t)m * n * 16, nB = (size_t)batch * m * 8, nX = (size_t)batch * n * 16,
-                 nY = (size_t)batch * m * 16, ws = ace_pipeline_workspace_size(cfg, batch, m, n);
-    std::vector<void*> bufs;
-    auto cleanup = [&]() {
-        for (void* q : bufs) (void)hipFree(q);
-        bufs.clear();
-    };
-    auto dalloc = [&](size_t bytes, void** q) -> hipError_t {
-        hipError_t e = hipMalloc(q, bytes);
-        if (e == hipSuccess) bufs.push_back(*q);
-        return e;
-    };
-    void *dA, *dB, *dX, *dY, *dQ, *dI, *dS, *dW;
-    hipError_t e;
-    if ((e = dalloc(nA, &dA)) || (e = dalloc(nB, &dB)) || (e = dalloc(nX, &dX)) || (e = dalloc(nY, &dY)) ||
-        (e = dalloc(8 * (size_t)batch, &dQ)) || (e = dalloc(4 * (size_t)batch * ld, &dI)) ||
-        (e = dalloc(4 * (size_t)batch, &dS)) || (e = dalloc(ws, &dW))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
-    }
-    int rc = ACE_OK;
-    if ((e = hipMemcpy(dA, A, nA, hipMemcpyHostToDevice)) || (e = hipMemcpy(dB, B, nB, hipMemcpyHostToDevice))) {
-        cleanup();
-        return fail(ACE_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    }
-    rc = ace_pipeline_solve_batch(cfg, batch, m, n, tx, rx, (const double*)dA, (const double*)dB, train_idx,
-                                  (double*)dX, (double*)dY, (double*)dQ, (int32_t*)dI, (uint32_t*)dS, dW, ws, nullptr);
-    if (rc == ACE_OK) {
-        if ((e = hipDeviceSynchronize()) || (e = hipMemcpy(X, dX, nX, hipMemcpyDeviceToHost)) ||
-            (e = hipMemcpy(Y, dY, nY, hipMemcpyDeviceToHost)) ||
-            (quality && (e = hipMemcpy(quality, dQ, 8 * (size_t)batch, hipMemcpyDeviceToHost))) ||
-            (stage_iters && (e = hipMemcpy(stage_iters, dI, 4 * (size_t)batch * ld, hipMemcpyDeviceToHost))) ||
-            (status && (e = hipMemcpy(status, dS, 4 * (size_t)batch, hipMemcpyDeviceToHost))))
-            rc = fail(ACE_ERR_HIP, "pipeline: %s", hipGetErrorString(e));
-    }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    return rc;
+    const size_t nX = (size_t)batch * n * 2, nY = (size_t)batch * m * 2,   // doubles
+                 ws = ace_pipeline_workspace_size(cfg, batch, m, n);
+    DevScope dev;
+    double *dA, *dB, *dX, *dY, *dQ;
+    int32_t* dI;
+    uint32_t* dS;
+    char* dW;
+    ACE_TRY(dev.put(&dA, A, (size_t)m * n * 2));
+    ACE_TRY(dev.put(&dB, B, (size_t)batch * m));
+    ACE_TRY(dev.alloc(&dX, nX));
+    ACE_TRY(dev.alloc(&dY, nY));
+    ACE_TRY(dev.alloc(&dQ, (size_t)batch));
+    ACE_TRY(dev.alloc(&dI, (size_t)batch * ld));
+    ACE_TRY(dev.alloc(&dS, (size_t)batch));
+    ACE_TRY(dev.alloc(&dW, ws));
+    ACE_TRY(ace_pipeline_solve_batch(cfg, batch, m, n, tx, rx, dA, dB, train_idx, dX, dY, dQ, dI, dS, dW, ws, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(dev.get(X, dX, nX));
+    ACE_TRY(dev.get(Y, dY, nY));
+    ACE_TRY(dev.get(quality, dQ, (size_t)batch));
+    ACE_TRY(dev.get(stage_iters, dI, (size_t)batch * ld));
+    return dev.get(status, dS, (size_t)batch);
 }
 
 }  // extern "C"

@@ -275,30 +275,18 @@ extern "C" int ace_rss_evaluate_host(int batch, int n, int Pt, const double* X, 
     g_err.clear();
     ACE_TRY(rs_check_args(batch, n, Pt, X, CB, rss, rss_shared, metrics));
     const size_t B = batch, P = Pt;
-    void* buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // X, CB, rss, metrics, pred, status
-    const size_t bytes[6] = {16 * B * n, 16 * P * n, 8 * (rss_shared ? 1 : B) * P, 32 * B, 8 * B * P, 4 * B};
-    const void* src[3] = {X, CB, rss};
-    auto cleanup = [&]() {
-        for (void* q : buf)
-            if (q) (void)hipFree(q);
-    };
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && e == hipSuccess; ++i)
-        if (i != 4 || pred) e = hipMalloc(&buf[i], bytes[i]);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipMemcpy(buf[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    int rc = ACE_OK;
-    if (e == hipSuccess)
-        rc = ace_rss_evaluate_batch(batch, n, Pt, (const double*)buf[0], (const double*)buf[1], (const double*)buf[2],
-                                    rss_shared, (double*)buf[3], (double*)buf[4], (uint32_t*)buf[5], nullptr);
-    if (e == hipSuccess && rc == ACE_OK) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(metrics, buf[3], bytes[3], hipMemcpyDeviceToHost);
-        if (e == hipSuccess && pred) e = hipMemcpy(pred, buf[4], bytes[4], hipMemcpyDeviceToHost);
-        if (e == hipSuccess && status) e = hipMemcpy(status, buf[5], bytes[5], hipMemcpyDeviceToHost);
-    }
-    const std::string keep = g_err;
-    cleanup();
-    g_err = keep;
-    if (e != hipSuccess) return fail(ACE_ERR_HIP, "rss_evaluate: %s", hipGetErrorString(e));
-    return rc;
+    DevScope d;
+    double *dX, *dCB, *drss, *dmet, *dpred = nullptr;
+    uint32_t* dst;
+    ACE_TRY(d.put(&dX, X, 2 * B * n));
+    ACE_TRY(d.put(&dCB, CB, 2 * P * n));
+    ACE_TRY(d.put(&drss, rss, (rss_shared ? 1 : B) * P));
+    ACE_TRY(d.alloc(&dmet, 4 * B));
+    if (pred) ACE_TRY(d.alloc(&dpred, B * P));
+    ACE_TRY(d.alloc(&dst, B));
+    ACE_TRY(ace_rss_evaluate_batch(batch, n, Pt, dX, dCB, drss, rss_shared, dmet, dpred, dst, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(d.get(metrics, dmet, 4 * B));
+    ACE_TRY(d.get(pred, dpred, B * P));
+    return d.get(status, dst, B);
 }

@@ -321,32 +321,24 @@ extern "C" int ace_beam_scan_host(int batch, int d0, int d1, int Q0, int Q1, con
     g_err.clear();
     ACE_TRY(sc_check_args(batch, d0, d1, Q0, Q1, X, W0, F1, K, top_pow, top_idx));
     const size_t B = batch, QQ = (size_t)Q0 * Q1;
-    // X, W0, F1, noise | top_pow, top_idx, total, power, status
-    void* buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[9] = {16 * B * d0 * d1, 16 * (size_t)Q0 * d0, 16 * (size_t)Q1 * d1, 16 * B * QQ, 8 * B * K,
-                             4 * B * K,        8 * B,                8 * B * QQ,           4 * B};
-    const void* src[4] = {X, W0, F1, noise};
-    void* dst[9] = {nullptr, nullptr, nullptr, nullptr, top_pow, top_idx, total, power, status};
-    const bool use[9] = {true, true, true, noise != nullptr, true, true, true, power != nullptr, true};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 9 && e == hipSuccess; ++i)
-        if (use[i]) e = hipMalloc(&buf[i], bytes[i]);
-    for (int i = 0; i < 4 && e == hipSuccess; ++i)
-        if (use[i]) e = hipMemcpy(buf[i], src[i], bytes[i], hipMemcpyHostToDevice);
-    int rc = ACE_OK;
-    if (e == hipSuccess)
-        rc = ace_beam_scan_batch(batch, d0, d1, Q0, Q1, (const double*)buf[0], (const double*)buf[1], (const double*)buf[2],
-                                 (const double*)buf[3], K, (double*)buf[4], (int32_t*)buf[5], (double*)buf[6],
-                                 (double*)buf[7], (uint32_t*)buf[8], nullptr);
-    if (e == hipSuccess && rc == ACE_OK) {
-        e = hipDeviceSynchronize();
-        for (int i = 4; i < 9 && e == hipSuccess; ++i)
-            if (use[i] && dst[i]) e = hipMemcpy(dst[i], buf[i], bytes[i], hipMemcpyDeviceToHost);
-    }
-    const std::string keep = g_err;
-    for (void* q : buf)
-        if (q) (void)hipFree(q);
-    g_err = keep;
-    if (e != hipSuccess) return fail(ACE_ERR_HIP, "beam_scan: %s", hipGetErrorString(e));
-    return rc;
+    DevScope d;
+    double *dX, *dW0, *dF1, *dnoise = nullptr, *dpow, *dtotal, *dpower = nullptr;
+    int32_t* didx;
+    uint32_t* dst;
+    ACE_TRY(d.put(&dX, X, 2 * B * d0 * d1));
+    ACE_TRY(d.put(&dW0, W0, 2 * (size_t)Q0 * d0));
+    ACE_TRY(d.put(&dF1, F1, 2 * (size_t)Q1 * d1));
+    if (noise) ACE_TRY(d.put(&dnoise, noise, 2 * B * QQ));
+    ACE_TRY(d.alloc(&dpow, B * K));
+    ACE_TRY(d.alloc(&didx, B * K));
+    ACE_TRY(d.alloc(&dtotal, B));
+    if (power) ACE_TRY(d.alloc(&dpower, B * QQ));
+    ACE_TRY(d.alloc(&dst, B));
+    ACE_TRY(ace_beam_scan_batch(batch, d0, d1, Q0, Q1, dX, dW0, dF1, dnoise, K, dpow, didx, dtotal, dpower, dst, nullptr));
+    ACE_HIP(hipDeviceSynchronize());
+    ACE_TRY(d.get(top_pow, dpow, B * K));
+    ACE_TRY(d.get(top_idx, didx, B * K));
+    ACE_TRY(d.get(total, dtotal, B));
+    ACE_TRY(d.get(power, dpower, B * QQ));
+    return d.get(status, dst, B);
 }

@@ -15,36 +15,6 @@
 namespace ace {
 namespace {
 
-struct DevPool {   // device allocations of one call, freed on scope exit
-    std::vector<void*> v;
-    ~DevPool() {
-        for (void* p : v) (void)hipFree(p);
-    }
-};
-
-// device array of `count` T holding src, or `fill` where src is null (at least one element is allocated)
-template <class T>
-int put(DevPool& pool, T** dst, const T* src, size_t count, T fill) {
-    void* p = nullptr;
-    ACE_HIP(hipMalloc(&p, sizeof(T) * (count ? count : 1)));
-    pool.v.push_back(p);
-    *dst = static_cast<T*>(p);
-    if (!count) return ACE_OK;
-    if (src) {
-        ACE_HIP(hipMemcpy(p, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    } else {
-        const std::vector<T> tmp(count, fill);
-        ACE_HIP(hipMemcpy(p, tmp.data(), sizeof(T) * count, hipMemcpyHostToDevice));
-    }
-    return ACE_OK;
-}
-template <class T>
-int get(T* dst, const T* src, size_t count) {
-    if (!dst || !count) return ACE_OK;
-    ACE_HIP(hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return ACE_OK;
-}
-
 const char* const kOpName[ACE_STAGE_NOPS] = {
     "init_r",      "ystep_r",      "finalize_r", "gram_rotate", "quality",     "part_quality", "keep_best",
     "finish",      "part_geinv",   "part_gfix",  "part_expand", "part_compact", "anorm",       "bnorm",
@@ -165,17 +135,17 @@ int stage_run(const ace_stage_args& a) {
     const size_t batch = (size_t)a.batch, n = (size_t)a.n, m = (size_t)a.m, r = (size_t)a.r;
     const double sv = a.sentinel;
     const int32_t si = a.isentinel;
-    DevPool pool;
+    DevScope d;
     hipStream_t st = nullptr;
     std::vector<RealState> rs;
     RealState* drs = nullptr;
     auto state_up = [&]() -> int {
         rs.resize(batch);
         fill_state(a, rs);
-        return put<RealState>(pool, &drs, rs.data(), batch, RealState{});
+        return d.put(&drs, rs.data(), batch, RealState{});
     };
     auto state_down = [&]() -> int {
-        ACE_TRY(get<RealState>(rs.data(), drs, batch));
+        ACE_TRY(d.get(rs.data(), drs, batch));
         read_state(a, rs);
         return ACE_OK;
     };
@@ -206,35 +176,35 @@ int stage_run(const ace_stage_args& a) {
         SG_NEED(B);
         const size_t bn = 2 * batch * r * n, bm = 2 * batch * r * m;
         unsigned char* dmask = nullptr;
-        if (a.mask) ACE_TRY(put<unsigned char>(pool, &dmask, a.mask, batch * m, 0));
+        if (a.mask) ACE_TRY(d.put(&dmask, a.mask, batch * m, 0));
         const PartRows pr{nullptr, dmask, nullptr, a.m, a.m, a.m};
         double *dB, *dYo, *dM;
-        ACE_TRY(put<double>(pool, &dB, a.B, batch * m, 0.0));
-        ACE_TRY(put<double>(pool, &dYo, nullptr, bm, sv));
+        ACE_TRY(d.put(&dB, a.B, batch * m, 0.0));
+        ACE_TRY(d.put(&dYo, nullptr, bm, sv));
         ACE_TRY(state_up());
         if (init) {
             double *dX0, *dP0, *dXo, *dNo;
-            ACE_TRY(put<double>(pool, &dX0, a.X, bn, 0.0));
-            ACE_TRY(put<double>(pool, &dP0, a.P0, bm, 0.0));
-            ACE_TRY(put<double>(pool, &dXo, nullptr, bn, sv));
-            ACE_TRY(put<double>(pool, &dNo, nullptr, bn, sv));
-            ACE_TRY(put<double>(pool, &dM, nullptr, bm, sv));
+            ACE_TRY(d.put(&dX0, a.X, bn, 0.0));
+            ACE_TRY(d.put(&dP0, a.P0, bm, 0.0));
+            ACE_TRY(d.put(&dXo, nullptr, bn, sv));
+            ACE_TRY(d.put(&dNo, nullptr, bn, sv));
+            ACE_TRY(d.put(&dM, nullptr, bm, sv));
             launch_init_r(a.row_mode, a.n, a.m, a.r, a.batch, dX0, dP0, dB, dXo, dYo, dM, dNo, drs, a.mu0, st,
                           a.mask ? &pr : nullptr);
             ACE_TRY(launched());
-            ACE_TRY(get(a.Xo, dXo, bn));
-            ACE_TRY(get(a.No, dNo, bn));
+            ACE_TRY(d.get(a.Xo, dXo, bn));
+            ACE_TRY(d.get(a.No, dNo, bn));
         } else {
             double *dS, *dg, *dYold;
-            ACE_TRY(put<double>(pool, &dS, a.S, bm, 0.0));
-            ACE_TRY(put<double>(pool, &dg, a.g, bm, 0.0));
-            ACE_TRY(put<double>(pool, &dM, a.M, bm, 0.0));
-            ACE_TRY(put<double>(pool, &dYold, a.Y, bm, 0.0));
+            ACE_TRY(d.put(&dS, a.S, bm, 0.0));
+            ACE_TRY(d.put(&dg, a.g, bm, 0.0));
+            ACE_TRY(d.put(&dM, a.M, bm, 0.0));
+            ACE_TRY(d.put(&dYold, a.Y, bm, 0.0));
             launch_ystep_r(a.row_mode, a.m, a.r, a.batch, dS, dg, dM, dB, dYold, dYo, drs, st, a.mask ? &pr : nullptr);
             ACE_TRY(launched());
         }
-        ACE_TRY(get(a.Yo, dYo, bm));
-        ACE_TRY(get(a.Mo, dM, bm));
+        ACE_TRY(d.get(a.Yo, dYo, bm));
+        ACE_TRY(d.get(a.Mo, dM, bm));
         return state_down();
     }
     case ACE_STAGE_FINALIZE_R: {
@@ -251,30 +221,30 @@ int stage_run(const ace_stage_args& a) {
         double *doX, *doY, *dX, *dY, *dXo, *dYo, *dmu, *dz1 = nullptr, *dz2 = nullptr, *dy1 = nullptr, *dy2 = nullptr;
         int32_t* dit;
         uint32_t* dst;
-        ACE_TRY(put<double>(pool, &doX, a.optX, on, 0.0));
-        ACE_TRY(put<double>(pool, &doY, a.optY, om, 0.0));
-        ACE_TRY(put<double>(pool, &dX, a.X, 2 * batch * r * n, 0.0));
-        ACE_TRY(put<double>(pool, &dY, a.Y, 2 * batch * r * m, 0.0));
-        if (a.Zb1) ACE_TRY(put<double>(pool, &dz1, a.Zb1, on, 0.0));
-        if (a.Zb2) ACE_TRY(put<double>(pool, &dz2, a.Zb2, on, 0.0));
-        if (a.Yb1) ACE_TRY(put<double>(pool, &dy1, a.Yb1, om, 0.0));
-        if (a.Yb2) ACE_TRY(put<double>(pool, &dy2, a.Yb2, om, 0.0));
-        ACE_TRY(put<double>(pool, &dXo, nullptr, on, sv));
-        ACE_TRY(put<double>(pool, &dYo, nullptr, om, sv));
-        ACE_TRY(put<double>(pool, &dmu, nullptr, batch, sv));
-        ACE_TRY(put<int32_t>(pool, &dit, nullptr, batch, si));
-        ACE_TRY(put<uint32_t>(pool, &dst, nullptr, batch, (uint32_t)si));
+        ACE_TRY(d.put(&doX, a.optX, on, 0.0));
+        ACE_TRY(d.put(&doY, a.optY, om, 0.0));
+        ACE_TRY(d.put(&dX, a.X, 2 * batch * r * n, 0.0));
+        ACE_TRY(d.put(&dY, a.Y, 2 * batch * r * m, 0.0));
+        if (a.Zb1) ACE_TRY(d.put(&dz1, a.Zb1, on, 0.0));
+        if (a.Zb2) ACE_TRY(d.put(&dz2, a.Zb2, on, 0.0));
+        if (a.Yb1) ACE_TRY(d.put(&dy1, a.Yb1, om, 0.0));
+        if (a.Yb2) ACE_TRY(d.put(&dy2, a.Yb2, om, 0.0));
+        ACE_TRY(d.put(&dXo, nullptr, on, sv));
+        ACE_TRY(d.put(&dYo, nullptr, om, sv));
+        ACE_TRY(d.put(&dmu, nullptr, batch, sv));
+        ACE_TRY(d.put(&dit, nullptr, batch, si));
+        ACE_TRY(d.put(&dst, nullptr, batch, (uint32_t)si));
         ACE_TRY(state_up());
         launch_finalize_r(a.n, a.m, a.r, a.nc, a.batch, doX, doY, dX, dY, dXo, dYo, dit, dst, dmu, drs, st, dz1, dz2, dy1,
                           dy2);
         ACE_TRY(launched());
-        ACE_TRY(get(a.Xo, dXo, on));
-        ACE_TRY(get(a.Yo, dYo, om));
-        ACE_TRY(get(a.qo, dmu, batch));
+        ACE_TRY(d.get(a.Xo, dXo, on));
+        ACE_TRY(d.get(a.Yo, dYo, om));
+        ACE_TRY(d.get(a.qo, dmu, batch));
         if (a.iout) {   // [batch][2]: iters, status
             std::vector<int32_t> it(batch), sb(batch);
-            ACE_TRY(get(it.data(), dit, batch));
-            ACE_TRY(get(reinterpret_cast<uint32_t*>(sb.data()), dst, batch));
+            ACE_TRY(d.get(it.data(), dit, batch));
+            ACE_TRY(d.get(reinterpret_cast<uint32_t*>(sb.data()), dst, batch));
             for (size_t b = 0; b < batch; ++b) {
                 a.iout[2 * b] = it[b];
                 a.iout[2 * b + 1] = sb[b];
@@ -289,12 +259,12 @@ int stage_run(const ace_stage_args& a) {
         SG_NEED(X);
         double* dX;
         int* dstat;
-        ACE_TRY(put<double>(pool, &dX, a.X, 2 * batch * r * n, 0.0));
-        ACE_TRY(put<int>(pool, &dstat, a.idst, batch, 0));
+        ACE_TRY(d.put(&dX, a.X, 2 * batch * r * n, 0.0));
+        ACE_TRY(d.put(&dstat, a.idst, batch, 0));
         launch_gram_rotate(a.n, a.r, a.batch, dX, dstat, st);
         ACE_TRY(launched());
-        ACE_TRY(get(a.Xo, dX, 2 * batch * r * n));
-        return get(a.iout, dstat, batch);
+        ACE_TRY(d.get(a.Xo, dX, 2 * batch * r * n));
+        return d.get(a.iout, dstat, batch);
     }
     case ACE_STAGE_QUALITY:
     case ACE_STAGE_PART_QUALITY: {
@@ -310,20 +280,20 @@ int stage_run(const ace_stage_args& a) {
         }
         const size_t rowsA = part ? m : (size_t)a.count;
         double *dA, *dX, *dB, *dq;
-        ACE_TRY(put<double>(pool, &dA, a.A, 2 * rowsA * n, 0.0));
-        ACE_TRY(put<double>(pool, &dX, a.X, 2 * batch * n, 0.0));
-        ACE_TRY(put<double>(pool, &dB, a.B, batch * rowsA, 0.0));
-        ACE_TRY(put<double>(pool, &dq, nullptr, batch, sv));
+        ACE_TRY(d.put(&dA, a.A, 2 * rowsA * n, 0.0));
+        ACE_TRY(d.put(&dX, a.X, 2 * batch * n, 0.0));
+        ACE_TRY(d.put(&dB, a.B, batch * rowsA, 0.0));
+        ACE_TRY(d.put(&dq, nullptr, batch, sv));
         if (part) {
             int* drows;
-            ACE_TRY(put<int>(pool, &drows, a.rows, batch * m, 0));
+            ACE_TRY(d.put(&drows, a.rows, batch * m, 0));
             const PartRows pr{drows, nullptr, nullptr, a.m, a.mt, a.m};
             launch_part_quality(a.n, a.batch, pr, dA, dX, dB, dq, st);
         } else {
             launch_quality(a.n, a.count, a.batch, dA, dX, dB, dq, st);
         }
         ACE_TRY(launched());
-        return get(a.qo, dq, batch);
+        return d.get(a.qo, dq, batch);
     }
     case ACE_STAGE_KEEP_BEST: {
         SG_RANGE(batch, 1, SG_MAXBATCH);
@@ -334,17 +304,17 @@ int stage_run(const ace_stage_args& a) {
         SG_NEED(X);
         SG_NEED(Y);
         double *dq, *dqm, *dX, *dY, *dXm, *dYm;
-        ACE_TRY(put<double>(pool, &dq, a.q, batch, 0.0));
-        ACE_TRY(put<double>(pool, &dqm, a.qmax, batch, 0.0));
-        ACE_TRY(put<double>(pool, &dX, a.X, 2 * batch * n, 0.0));
-        ACE_TRY(put<double>(pool, &dY, a.Y, 2 * batch * m, 0.0));
-        ACE_TRY(put<double>(pool, &dXm, a.Xmax, 2 * batch * n, sv));
-        ACE_TRY(put<double>(pool, &dYm, a.Ymax, 2 * batch * m, sv));
+        ACE_TRY(d.put(&dq, a.q, batch, 0.0));
+        ACE_TRY(d.put(&dqm, a.qmax, batch, 0.0));
+        ACE_TRY(d.put(&dX, a.X, 2 * batch * n, 0.0));
+        ACE_TRY(d.put(&dY, a.Y, 2 * batch * m, 0.0));
+        ACE_TRY(d.put(&dXm, a.Xmax, 2 * batch * n, sv));
+        ACE_TRY(d.put(&dYm, a.Ymax, 2 * batch * m, sv));
         launch_keep_best(a.n, a.m, a.batch, a.first != 0, dq, dqm, dX, dY, dXm, dYm, st);
         ACE_TRY(launched());
-        ACE_TRY(get(a.qo, dqm, batch));
-        ACE_TRY(get(a.Xo, dXm, 2 * batch * n));
-        return get(a.Yo, dYm, 2 * batch * m);
+        ACE_TRY(d.get(a.qo, dqm, batch));
+        ACE_TRY(d.get(a.Xo, dXm, 2 * batch * n));
+        return d.get(a.Yo, dYm, 2 * batch * m);
     }
     case ACE_STAGE_FINISH: {
         SG_RANGE(batch, 1, SG_MAXBATCH);
@@ -360,21 +330,21 @@ int stage_run(const ace_stage_args& a) {
         SG_NEED(bnorm);
         double *dq, *dX, *dY, *dXm, *dYm, *dan, *dbn, *dXo, *dYo;
         uint32_t* dstat;
-        ACE_TRY(put<double>(pool, &dq, a.q, batch, 0.0));
-        ACE_TRY(put<double>(pool, &dX, a.X, 2 * batch * n, 0.0));
-        ACE_TRY(put<double>(pool, &dY, a.Y, 2 * batch * m, 0.0));
-        ACE_TRY(put<double>(pool, &dXm, a.Xmax, 2 * batch * n, 0.0));
-        ACE_TRY(put<double>(pool, &dYm, a.Ymax, 2 * batch * (size_t)a.mt, 0.0));
-        ACE_TRY(put<double>(pool, &dan, a.anorm, 1, 0.0));
-        ACE_TRY(put<double>(pool, &dbn, a.bnorm, batch, 0.0));
-        ACE_TRY(put<double>(pool, &dXo, nullptr, 2 * batch * n, sv));
-        ACE_TRY(put<double>(pool, &dYo, nullptr, 2 * batch * m, sv));
-        ACE_TRY(put<uint32_t>(pool, &dstat, reinterpret_cast<const uint32_t*>(a.idst), batch, 0u));
+        ACE_TRY(d.put(&dq, a.q, batch, 0.0));
+        ACE_TRY(d.put(&dX, a.X, 2 * batch * n, 0.0));
+        ACE_TRY(d.put(&dY, a.Y, 2 * batch * m, 0.0));
+        ACE_TRY(d.put(&dXm, a.Xmax, 2 * batch * n, 0.0));
+        ACE_TRY(d.put(&dYm, a.Ymax, 2 * batch * (size_t)a.mt, 0.0));
+        ACE_TRY(d.put(&dan, a.anorm, 1, 0.0));
+        ACE_TRY(d.put(&dbn, a.bnorm, batch, 0.0));
+        ACE_TRY(d.put(&dXo, nullptr, 2 * batch * n, sv));
+        ACE_TRY(d.put(&dYo, nullptr, 2 * batch * m, sv));
+        ACE_TRY(d.put(&dstat, reinterpret_cast<const uint32_t*>(a.idst), batch, 0u));
         launch_finish(a.n, a.m, a.mt, a.batch, dq, dX, dY, dXm, dYm, dan, dbn, dXo, dYo, dstat, st);
         ACE_TRY(launched());
-        ACE_TRY(get(a.Xo, dXo, 2 * batch * n));
-        ACE_TRY(get(a.Yo, dYo, 2 * batch * m));
-        return get(reinterpret_cast<uint32_t*>(a.iout), dstat, batch);
+        ACE_TRY(d.get(a.Xo, dXo, 2 * batch * n));
+        ACE_TRY(d.get(a.Yo, dYo, 2 * batch * m));
+        return d.get(reinterpret_cast<uint32_t*>(a.iout), dstat, batch);
     }
     case ACE_STAGE_PART_GEINV:
     case ACE_STAGE_PART_GFIX: {
@@ -395,28 +365,28 @@ int stage_run(const ace_stage_args& a) {
         }
         double *dG, *dgi;
         int* drows;
-        ACE_TRY(put<double>(pool, &dG, a.G, 2 * m * m, 0.0));
-        ACE_TRY(put<int>(pool, &drows, a.rows, batch * m, 0));
+        ACE_TRY(d.put(&dG, a.G, 2 * m * m, 0.0));
+        ACE_TRY(d.put(&drows, a.rows, batch * m, 0));
         if (!fix) {
             int* dstat;
-            ACE_TRY(put<double>(pool, &dgi, nullptr, 2 * batch * te * te, sv));
-            ACE_TRY(put<int>(pool, &dstat, a.idst, batch, 0));
+            ACE_TRY(d.put(&dgi, nullptr, 2 * batch * te * te, sv));
+            ACE_TRY(d.put(&dstat, a.idst, batch, 0));
             const PartRows pr{drows, nullptr, dgi, a.m, a.mt, a.m};
             launch_part_geinv(a.batch, pr, dG, dgi, dstat, st);
             ACE_TRY(launched());
-            ACE_TRY(get(a.Xo, dgi, 2 * batch * te * te));
-            return get(a.iout, dstat, batch);
+            ACE_TRY(d.get(a.Xo, dgi, 2 * batch * te * te));
+            return d.get(a.iout, dstat, batch);
         }
         unsigned char* dmask;
         double* dg;
-        ACE_TRY(put<double>(pool, &dgi, a.geinv, 2 * batch * te * te, 0.0));
-        ACE_TRY(put<unsigned char>(pool, &dmask, a.mask, batch * m, 0));
-        ACE_TRY(put<double>(pool, &dg, a.g, 2 * batch * r * m, 0.0));
+        ACE_TRY(d.put(&dgi, a.geinv, 2 * batch * te * te, 0.0));
+        ACE_TRY(d.put(&dmask, a.mask, batch * m, 0));
+        ACE_TRY(d.put(&dg, a.g, 2 * batch * r * m, 0.0));
         if (a.flags) ACE_TRY(state_up());
         const PartRows pr{drows, dmask, dgi, a.m, a.mt, a.m};
         launch_part_gfix(a.batch, a.r, pr, dG, dg, a.flags ? drs : nullptr, st);
         ACE_TRY(launched());
-        return get(a.Yo, dg, 2 * batch * r * m);
+        return d.get(a.Yo, dg, 2 * batch * r * m);
     }
     case ACE_STAGE_PART_EXPAND:
     case ACE_STAGE_PART_COMPACT: {
@@ -428,38 +398,38 @@ int stage_run(const ace_stage_args& a) {
         const size_t cm = 2 * batch * r * (size_t)a.mt, fm = 2 * batch * r * m;
         double *dsrc, *ddst;
         int* drows;
-        ACE_TRY(put<int>(pool, &drows, a.rows, batch * m, 0));
-        ACE_TRY(put<double>(pool, &dsrc, a.Y, expand ? cm : fm, 0.0));
-        ACE_TRY(put<double>(pool, &ddst, nullptr, expand ? fm : cm, sv));
+        ACE_TRY(d.put(&drows, a.rows, batch * m, 0));
+        ACE_TRY(d.put(&dsrc, a.Y, expand ? cm : fm, 0.0));
+        ACE_TRY(d.put(&ddst, nullptr, expand ? fm : cm, sv));
         const PartRows pr{drows, nullptr, nullptr, a.m, a.mt, a.m};
         if (expand) launch_part_expand(a.batch, a.r, pr, dsrc, ddst, st);
         else launch_part_compact(a.batch, a.r, pr, dsrc, ddst, st);
         ACE_TRY(launched());
-        return get(a.Yo, ddst, expand ? fm : cm);
+        return d.get(a.Yo, ddst, expand ? fm : cm);
     }
     case ACE_STAGE_ANORM: {
         SG_RANGE(m, 1, SG_MAXDIM);
         SG_RANGE(n, 1, SG_MAXDIM);
         SG_NEED(A);
         double *dA, *dq;
-        ACE_TRY(put<double>(pool, &dA, a.A, 2 * m * n, 0.0));
-        ACE_TRY(put<double>(pool, &dq, nullptr, 1, sv));
+        ACE_TRY(d.put(&dA, a.A, 2 * m * n, 0.0));
+        ACE_TRY(d.put(&dq, nullptr, 1, sv));
         launch_anorm(a.m, a.n, dA, a.tol_abs, dq, st);
         ACE_TRY(launched());
-        return get(a.qo, dq, 1);
+        return d.get(a.qo, dq, 1);
     }
     case ACE_STAGE_BNORM: {
         SG_RANGE(batch, 1, SG_MAXBATCH);
         SG_RANGE(m, 1, SG_MAXDIM);
         SG_NEED(B);
         double *dB, *dq, *dBn;
-        ACE_TRY(put<double>(pool, &dB, a.B, batch * m, 0.0));
-        ACE_TRY(put<double>(pool, &dq, nullptr, batch, sv));
-        ACE_TRY(put<double>(pool, &dBn, nullptr, batch * m, sv));
+        ACE_TRY(d.put(&dB, a.B, batch * m, 0.0));
+        ACE_TRY(d.put(&dq, nullptr, batch, sv));
+        ACE_TRY(d.put(&dBn, nullptr, batch * m, sv));
         launch_bnorm(a.m, a.batch, dB, a.tol_abs, dq, dBn, st);
         ACE_TRY(launched());
-        ACE_TRY(get(a.qo, dq, batch));
-        return get(a.Xo, dBn, batch * m);
+        ACE_TRY(d.get(a.qo, dq, batch));
+        return d.get(a.Xo, dBn, batch * m);
     }
     case ACE_STAGE_GATHER_ROWS: {
         SG_RANGE(m, 1, SG_MAXDIM);
@@ -471,13 +441,13 @@ int stage_run(const ace_stage_args& a) {
         ACE_TRY(check_idx(a, a.count, a.m, false));
         double *dA, *dan, *dd;
         int* didx;
-        ACE_TRY(put<double>(pool, &dA, a.A, 2 * m * n, 0.0));
-        ACE_TRY(put<double>(pool, &dan, a.anorm, 1, 0.0));
-        ACE_TRY(put<int>(pool, &didx, a.idx, (size_t)a.count, 0));
-        ACE_TRY(put<double>(pool, &dd, nullptr, 2 * (size_t)a.count * n, sv));
+        ACE_TRY(d.put(&dA, a.A, 2 * m * n, 0.0));
+        ACE_TRY(d.put(&dan, a.anorm, 1, 0.0));
+        ACE_TRY(d.put(&didx, a.idx, (size_t)a.count, 0));
+        ACE_TRY(d.put(&dd, nullptr, 2 * (size_t)a.count * n, sv));
         launch_gather_rows(a.count, a.n, dA, didx, dan, dd, st);
         ACE_TRY(launched());
-        return get(a.Xo, dd, 2 * (size_t)a.count * n);
+        return d.get(a.Xo, dd, 2 * (size_t)a.count * n);
     }
     case ACE_STAGE_GATHER_B: {
         SG_RANGE(batch, 1, SG_MAXBATCH);
@@ -488,12 +458,12 @@ int stage_run(const ace_stage_args& a) {
         ACE_TRY(check_idx(a, a.count, a.m, false));
         double *dB, *dd;
         int* didx;
-        ACE_TRY(put<double>(pool, &dB, a.B, batch * m, 0.0));
-        ACE_TRY(put<int>(pool, &didx, a.idx, (size_t)a.count, 0));
-        ACE_TRY(put<double>(pool, &dd, nullptr, batch * (size_t)a.count, sv));
+        ACE_TRY(d.put(&dB, a.B, batch * m, 0.0));
+        ACE_TRY(d.put(&didx, a.idx, (size_t)a.count, 0));
+        ACE_TRY(d.put(&dd, nullptr, batch * (size_t)a.count, sv));
         launch_gather_b(a.m, a.count, a.batch, dB, didx, dd, st);
         ACE_TRY(launched());
-        return get(a.qo, dd, batch * (size_t)a.count);
+        return d.get(a.qo, dd, batch * (size_t)a.count);
     }
     case ACE_STAGE_MOVE_ROWS:
     case ACE_STAGE_MOVE_BYTES: {
@@ -509,21 +479,21 @@ int stage_run(const ace_stage_args& a) {
         ACE_TRY(check_idx(a, a.count, a.m, sc));
         const size_t len = (size_t)a.len, ns = (sc ? (size_t)a.count : m) * len, nd = (sc ? m : (size_t)a.count) * len;
         int* didx;
-        ACE_TRY(put<int>(pool, &didx, a.idx, (size_t)a.count, 0));
+        ACE_TRY(d.put(&didx, a.idx, (size_t)a.count, 0));
         if (bytes) {
             unsigned char *ds, *dd;
-            ACE_TRY(put<unsigned char>(pool, &ds, a.bsrc, ns, 0));
-            ACE_TRY(put<unsigned char>(pool, &dd, nullptr, nd, (unsigned char)si));
+            ACE_TRY(d.put(&ds, a.bsrc, ns, 0));
+            ACE_TRY(d.put(&dd, nullptr, nd, (unsigned char)si));
             launch_move_bytes(a.count, a.len, ds, dd, didx, sc, st);
             ACE_TRY(launched());
-            return get(a.bout, dd, nd);
+            return d.get(a.bout, dd, nd);
         }
         double *ds, *dd;
-        ACE_TRY(put<double>(pool, &ds, a.src, ns, 0.0));
-        ACE_TRY(put<double>(pool, &dd, nullptr, nd, sv));
+        ACE_TRY(d.put(&ds, a.src, ns, 0.0));
+        ACE_TRY(d.put(&dd, nullptr, nd, sv));
         launch_move_rows(a.count, a.len, ds, dd, didx, sc, st);
         ACE_TRY(launched());
-        return get(a.qo, dd, nd);
+        return d.get(a.qo, dd, nd);
     }
     case ACE_STAGE_PUT_COL: {
         // dst [m][ld] int32 (idst, or isentinel), count <= (idx ? any : m) sources
@@ -534,12 +504,12 @@ int stage_run(const ace_stage_args& a) {
         if (a.count) SG_NEED(isrc);
         if (a.idx) ACE_TRY(check_idx(a, a.count, a.m, true));
         int *ds, *didx = nullptr, *dd;
-        ACE_TRY(put<int>(pool, &ds, a.isrc, (size_t)a.count, 0));
-        if (a.idx) ACE_TRY(put<int>(pool, &didx, a.idx, (size_t)a.count, 0));
-        ACE_TRY(put<int>(pool, &dd, a.idst, m * (size_t)a.ld, si));
+        ACE_TRY(d.put(&ds, a.isrc, (size_t)a.count, 0));
+        if (a.idx) ACE_TRY(d.put(&didx, a.idx, (size_t)a.count, 0));
+        ACE_TRY(d.put(&dd, a.idst, m * (size_t)a.ld, si));
         launch_put_col(a.count, ds, didx, dd, a.ld, a.col, a.or_mask, st);
         ACE_TRY(launched());
-        return get(a.iout, dd, m * (size_t)a.ld);
+        return d.get(a.iout, dd, m * (size_t)a.ld);
     }
     case ACE_STAGE_FLAG_BITS: {
         // dst [m] int32 (idst, or isentinel), flag [count], count <= m
@@ -548,21 +518,21 @@ int stage_run(const ace_stage_args& a) {
         if (a.count) SG_NEED(bsrc);
         unsigned char* df;
         int* dd;
-        ACE_TRY(put<unsigned char>(pool, &df, a.bsrc, (size_t)a.count, 0));
-        ACE_TRY(put<int>(pool, &dd, a.idst, m, si));
+        ACE_TRY(d.put(&df, a.bsrc, (size_t)a.count, 0));
+        ACE_TRY(d.put(&dd, a.idst, m, si));
         launch_flag_bits(a.count, df, dd, a.bit, st);
         ACE_TRY(launched());
-        return get(a.iout, dd, m);
+        return d.get(a.iout, dd, m);
     }
     case ACE_STAGE_FILL: {
         // dst [m] doubles of sentinel, the first len set to value
         SG_RANGE(m, 1, 1 << 24);
         SG_RANGE(len, 0, a.m);
         double* dd;
-        ACE_TRY(put<double>(pool, &dd, nullptr, m, sv));
+        ACE_TRY(d.put(&dd, nullptr, m, sv));
         launch_fill(a.len, a.value, dd, st);
         ACE_TRY(launched());
-        return get(a.qo, dd, m);
+        return d.get(a.qo, dd, m);
     }
     }
     return fail(ACE_ERR_ARG, "ace_stage_host: unknown op %d", a.op);

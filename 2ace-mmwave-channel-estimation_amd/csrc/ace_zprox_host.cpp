@@ -14,30 +14,6 @@
 namespace ace {
 namespace {
 
-struct DevBuf {   // one device allocation, freed on scope exit
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-int h2d(void* dst, const void* src, size_t bytes) {
-    if (!bytes) return ACE_OK;
-    ACE_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return ACE_OK;
-}
-int d2h(void* dst, const void* src, size_t bytes) {
-    if (!bytes || !dst) return ACE_OK;
-    ACE_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return ACE_OK;
-}
-// device buffer of `count` doubles holding src, or `fill` where src is null
-int put(double* dst, const double* src, size_t count, double fill, std::vector<double>& tmp) {
-    if (src) return h2d(dst, src, 8 * count);
-    tmp.assign(count, fill);
-    return h2d(dst, tmp.data(), 8 * count);
-}
-
 int zprox_run(const ace_zprox_args& a) {
     const int batch = a.batch, tx = a.tx, rx = a.rx, r = a.r, m = a.m;
     const bool init = a.init != 0, pp = a.pingpong != 0, wmode = a.wmode != 0;
@@ -86,13 +62,8 @@ int zprox_run(const ace_zprox_args& a) {
         ddone = cv.take<int>(256);
         dr1 = cv.take<unsigned char>((size_t)batch);
     };
-    Carver measure{nullptr};
-    carve(measure);
-    DevBuf ws;
-    ACE_HIP(hipMalloc(&ws.p, measure.off));
-    ACE_HIP(hipMemset(ws.p, 0, measure.off));
-    Carver cv{static_cast<char*>(ws.p)};
-    carve(cv);
+    DevScope d;
+    ACE_TRY(carve_zeroed(d, carve));
     hipStream_t st = nullptr;
 
     std::vector<RealState> rs((size_t)batch);
@@ -123,17 +94,16 @@ int zprox_run(const ace_zprox_args& a) {
             s.optsrc = f[3];
         }
     }
-    ACE_TRY(h2d(drs, rs.data(), sizeof(RealState) * rs.size()));
-    std::vector<double> tmp;
-    ACE_TRY(h2d(dX, a.X, 8 * bn));
-    ACE_TRY(put(dZ, a.Z, bn, 0.0, tmp));
-    ACE_TRY(put(dN, a.N, bn, 0.0, tmp));
-    ACE_TRY(put(dZ2, nullptr, bn, a.sentinel, tmp));
-    ACE_TRY(put(dN2, nullptr, bn, a.sentinel, tmp));
-    ACE_TRY(put(dQ, a.Q, bq, a.sentinel, tmp));
-    ACE_TRY(put(doptX, nullptr, bo, a.sentinel, tmp));
-    ACE_TRY(put(dXcur, nullptr, bn, a.sentinel, tmp));
-    if (a.rank_one) ACE_TRY(h2d(dr1, a.rank_one, (size_t)batch));
+    ACE_TRY(d.set(drs, rs.data(), rs.size()));
+    ACE_TRY(d.set(dX, a.X, bn));
+    ACE_TRY(d.set(dZ, a.Z, bn, 0.0));
+    ACE_TRY(d.set(dN, a.N, bn, 0.0));
+    ACE_TRY(d.set(dZ2, nullptr, bn, a.sentinel));
+    ACE_TRY(d.set(dN2, nullptr, bn, a.sentinel));
+    ACE_TRY(d.set(dQ, a.Q, bq, a.sentinel));
+    ACE_TRY(d.set(doptX, nullptr, bo, a.sentinel));
+    ACE_TRY(d.set(dXcur, nullptr, bn, a.sentinel));
+    if (a.rank_one) ACE_TRY(d.set(dr1, a.rank_one, (size_t)batch));
 
     ZArgs za{};
     za.n = n;
@@ -193,12 +163,12 @@ int zprox_run(const ace_zprox_args& a) {
     ACE_LAUNCHED("ace_zprox_host");
     ACE_HIP(hipDeviceSynchronize());
 
-    ACE_TRY(d2h(a.Zo, pp ? dZ2 : dZ, 8 * bn));
-    ACE_TRY(d2h(a.No, pp ? dN2 : dN, 8 * bn));
-    ACE_TRY(d2h(a.Qo, dQ, 8 * bq));
-    ACE_TRY(d2h(a.optX, doptX, 8 * bo));
-    ACE_TRY(d2h(a.Xcur, dXcur, 8 * bo));
-    ACE_TRY(d2h(rs.data(), drs, sizeof(RealState) * rs.size()));
+    ACE_TRY(d.get(a.Zo, pp ? dZ2 : dZ, bn));
+    ACE_TRY(d.get(a.No, pp ? dN2 : dN, bn));
+    ACE_TRY(d.get(a.Qo, dQ, bq));
+    ACE_TRY(d.get(a.optX, doptX, bo));
+    ACE_TRY(d.get(a.Xcur, dXcur, bo));
+    ACE_TRY(d.get(rs.data(), drs, rs.size()));
     for (int b = 0; b < batch; ++b) {
         const RealState& s = rs[b];
         if (a.state_out) {
@@ -222,7 +192,7 @@ int zprox_run(const ace_zprox_args& a) {
             f[7] = s.zit;
         }
     }
-    if (a.tkcnt) ACE_TRY(d2h(a.tkcnt, ddone + 32, 2 * sizeof(int32_t)));
+    if (a.tkcnt) ACE_TRY(d.get(a.tkcnt, ddone + 32, 2));
     return ACE_OK;
 }
 

@@ -3,10 +3,13 @@
 // translation unit is compiled with -fsanitize=address,undefined (device code is not
 // instrumented), linked with this driver into tests/native/ace_capi_sanitize.
 //
-//   ace_capi_sanitize cpu   host-only entry points and the argument checks that return before
-//                           any device call (runs without a GPU: tests/test_sanitize.py)
-//   ace_capi_sanitize gpu   the above plus small solves through every *_host wrapper, the driver
-//                           and the beamformer (tests/test_gpu_sanitize.py)
+//   ace_capi_sanitize cpu   host-only entry points, the argument checks that return before any
+//                           device call, and one valid call of every host-array entry: without a
+//                           GPU each comes back through its HIP-failure exit (ACE_ERR_HIP, with a
+//                           text), with one it succeeds (tests/test_sanitize.py)
+//   ace_capi_sanitize gpu   the above, every call required to succeed, plus small solves through
+//                           the solver wrappers, the driver and the beamformer
+//                           (tests/test_gpu_sanitize.py)
 // Any sanitizer report aborts with a non-zero exit; the program prints "OK" at the end.
 #include <cmath>
 #include <complex>
@@ -22,6 +25,7 @@
 namespace {
 
 int g_fail = 0;
+bool g_gpu = false;
 #define CHECK(c)                                                                  \
     do {                                                                          \
         if (!(c)) {                                                               \
@@ -152,6 +156,286 @@ void host_only() {
     CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 3, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
     CHECK(ace_zgemm_host(1, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 2, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
     CHECK(ace_zgemm_host(0, 0, 2, 2, 2, &d, 4, 2, 0, &d, 4, 1, 0, &d, nullptr, 4, 2, 0, 1, nullptr, 0, 0) == ACE_ERR_ARG);
+}
+
+// The return of a valid host-array call: ACE_OK (true), or without a GPU ACE_ERR_HIP and its text.
+bool ran(int rc) {
+    if (rc == ACE_OK) return true;
+    CHECK(!g_gpu && rc == ACE_ERR_HIP && strlen(ace_last_error()) > 0);
+    return false;
+}
+
+// One valid call of every host-array entry at a small shape (optional arrays both ways).
+void host_entries() {
+    const int tx = 4, rx = 4, n = 16, batch = 3;
+    const auto X = cvec((size_t)batch * n);
+    std::vector<uint32_t> st(batch);
+    // ---- evaluation: channel metrics, held-out RSS (8 probes)
+    {
+        const auto G = cvec((size_t)batch * n);
+        std::vector<double> met(4 * (size_t)batch);
+        if (ran(ace_evaluate_host(batch, tx, rx, X.data(), G.data(), met.data(), st.data()))) CHECK(finite(met));
+        const int Pt = 8;
+        const auto CB = cvec((size_t)Pt * n);
+        const auto rss = magnitudes(CB, G, batch, Pt, n);
+        std::vector<double> pred((size_t)batch * Pt);
+        if (ran(ace_rss_evaluate_host(batch, n, Pt, X.data(), CB.data(), rss.data(), 0, met.data(), pred.data(), st.data())))
+            CHECK(finite(met) && finite(pred));
+        if (ran(ace_rss_evaluate_host(batch, n, Pt, X.data(), CB.data(), rss.data(), 0, met.data(), nullptr, nullptr)))
+            CHECK(finite(met));
+    }
+    // ---- beam scan: K = 1 and 4, without and with noise / power
+    {
+        const int Q = 8, QQ = Q * Q;
+        const auto W0 = cvec((size_t)Q * tx), F1 = cvec((size_t)Q * rx), noise = cvec((size_t)batch * QQ);
+        for (int K : {1, 4})
+            for (int full = 0; full < 2; ++full) {
+                std::vector<double> tp((size_t)batch * K), total(batch), power((size_t)batch * QQ);
+                std::vector<int32_t> ti((size_t)batch * K);
+                if (ran(ace_beam_scan_host(batch, tx, rx, Q, Q, X.data(), W0.data(), F1.data(), full ? noise.data() : nullptr,
+                                           K, tp.data(), ti.data(), full ? total.data() : nullptr,
+                                           full ? power.data() : nullptr, full ? st.data() : nullptr))) {
+                    CHECK(finite(tp) && finite(total) && finite(power));
+                    for (int v : ti) CHECK(v >= 0 && v < QQ);
+                }
+            }
+    }
+    // ---- sparse stages: OMP and EM-BG-GAMP on a 2-sparse signal, optional arrays both ways
+    {
+        const int d = 16, N = 32, kmax = 2;
+        const auto D = cvec((size_t)d * N);
+        std::vector<double> xs(2 * (size_t)batch * N, 0.0);
+        for (int b = 0; b < batch; ++b) xs[2 * ((size_t)b * N + 3 + b)] = 1.0, xs[2 * ((size_t)b * N + 20) + 1] = -0.7;
+        std::vector<double> Y(2 * (size_t)batch * d);   // Y_b = D x_b
+        for (int b = 0; b < batch; ++b)
+            for (int i = 0; i < d; ++i) {
+                std::complex<double> acc = 0;
+                for (int k = 0; k < N; ++k)
+                    acc += std::complex<double>(D[2 * ((size_t)i * N + k)], D[2 * ((size_t)i * N + k) + 1]) *
+                           std::complex<double>(xs[2 * ((size_t)b * N + k)], xs[2 * ((size_t)b * N + k) + 1]);
+                Y[2 * ((size_t)b * d + i)] = acc.real();
+                Y[2 * ((size_t)b * d + i) + 1] = acc.imag();
+            }
+        const std::vector<double> cs(N, 1.0);
+        for (int full = 0; full < 2; ++full) {
+            std::vector<int32_t> idx((size_t)batch * kmax), cnt(batch);
+            std::vector<double> coef(2 * (size_t)batch * kmax), res(batch), x(2 * (size_t)batch * N);
+            if (ran(ace_omp_solve_host(batch, d, N, kmax, 1e-12, D.data(), full ? cs.data() : nullptr, Y.data(), idx.data(),
+                                       coef.data(), cnt.data(), res.data(), full ? st.data() : nullptr,
+                                       full ? x.data() : nullptr))) {
+                CHECK(finite(coef) && finite(res) && finite(x));
+                for (int v : cnt) CHECK(v >= 0 && v <= kmax);
+            }
+            ace_gamp_cfg gc;
+            ace_gamp_cfg_default(&gc);
+            gc.snr_db = 20.0;
+            gc.lambda0 = 2.0 / N;
+            gc.max_em_iter = 2;
+            gc.gamp_nit = 5;
+            std::vector<double> xh(2 * (size_t)batch * N), xv((size_t)batch * N), par(3 * (size_t)batch);
+            std::vector<int32_t> em(batch), tr(2 * (size_t)batch * (gc.max_em_iter + 1));
+            if (ran(ace_gamp_solve_host(&gc, batch, d, N, D.data(), Y.data(), xh.data(), full ? xv.data() : nullptr,
+                                        par.data(), em.data(), full ? tr.data() : nullptr, full ? st.data() : nullptr))) {
+                CHECK(finite(xh) && finite(xv) && finite(par));
+                for (int v : em) CHECK(v >= 0 && v <= gc.max_em_iter);
+            }
+        }
+    }
+    // ---- one cold init Z-step, r = 1 (one-wave kernel) and r = 2 (four-wave kernel)
+    for (int r : {1, 2}) {
+        const auto Xr = cvec((size_t)batch * r * n);
+        std::vector<double> Zo(2 * (size_t)batch * r * n), No(Zo.size()), Qo(2 * (size_t)batch * tx * tx), oX(Zo.size()),
+            Xc(Zo.size()), so((size_t)batch * ACE_ZP_NOUT);
+        std::vector<int32_t> fo((size_t)batch * ACE_ZP_NFLAGOUT), tk(2);
+        ace_zprox_args za{};
+        za.variant = ACE_VARIANT_A2ONLY;
+        za.batch = batch;
+        za.tx = tx;
+        za.rx = rx;
+        za.r = r;
+        za.m = 16;
+        za.init = 1;
+        za.row_mode = 1;
+        za.tol_rel = 1e-4;
+        za.tol_abs = 1e-8;
+        za.rho = 1.03;
+        za.sentinel = -3.0;
+        za.X = Xr.data();
+        za.Zo = Zo.data();
+        za.No = No.data();
+        za.Qo = Qo.data();
+        za.optX = oX.data();
+        za.Xcur = Xc.data();
+        za.state_out = so.data();
+        za.flags_out = fo.data();
+        za.tkcnt = tk.data();
+        if (ran(ace_zprox_host(&za))) CHECK(finite(Zo) && finite(No) && finite(Qo) && finite(oX) && finite(Xc) && finite(so));
+    }
+    // ---- stage kernels: fill, gather_rows, init_r
+    {
+        const int sb = 2, m = 12, r = 2;
+        std::vector<double> q(m);
+        ace_stage_args f{};
+        f.op = ACE_STAGE_FILL;
+        f.m = m;
+        f.len = 5;
+        f.value = 2.5;
+        f.sentinel = -3.0;
+        f.qo = q.data();
+        if (ran(ace_stage_host(&f))) CHECK(q[4] == 2.5 && q[5] == -3.0);
+        const auto A = cvec((size_t)m * n);
+        const int32_t idx[3] = {0, 5, 11};
+        const double anorm = 1.0;
+        std::vector<double> rows(2 * (size_t)3 * n);
+        ace_stage_args g{};
+        g.op = ACE_STAGE_GATHER_ROWS;
+        g.m = m;
+        g.n = n;
+        g.count = 3;
+        g.A = A.data();
+        g.idx = idx;
+        g.anorm = &anorm;
+        g.sentinel = -3.0;
+        g.Xo = rows.data();
+        if (ran(ace_stage_host(&g))) CHECK(finite(rows) && rows[0] == A[0]);
+        const auto X0 = cvec((size_t)sb * r * n), P0 = cvec((size_t)sb * r * m);
+        std::vector<double> B((size_t)sb * m);
+        for (auto& v : B) v = 0.5 + uni();
+        std::vector<double> Xo(2 * (size_t)sb * r * n), No(Xo.size()), Yo(2 * (size_t)sb * r * m), Mo(Yo.size()),
+            so((size_t)sb * ACE_SG_NSTATE);
+        std::vector<int32_t> fo((size_t)sb * ACE_SG_NFLAG);
+        ace_stage_args a{};
+        a.op = ACE_STAGE_INIT_R;
+        a.row_mode = 1;
+        a.batch = sb;
+        a.n = n;
+        a.m = m;
+        a.r = r;
+        a.mu0 = 1e-3;
+        a.sentinel = -3.0;
+        a.X = X0.data();
+        a.P0 = P0.data();
+        a.B = B.data();
+        a.Xo = Xo.data();
+        a.No = No.data();
+        a.Yo = Yo.data();
+        a.Mo = Mo.data();
+        a.state_out = so.data();
+        a.flags_out = fo.data();
+        // (state_out: mu, then last_res and opt_obj, which start at infinity)
+        if (ran(ace_stage_host(&a))) CHECK(finite(Xo) && finite(No) && finite(Yo) && finite(Mo) && std::isfinite(so[0]));
+    }
+    // ---- spectral initialisation, the prox's eigensolver, PhaseLift with its iterate
+    {
+        const int m = 48, r = 2;
+        const auto A = codebook(m, n);
+        const auto B = magnitudes(A, X, batch, m, n);
+        std::vector<double> Xs(2 * (size_t)batch * r * n);
+        if (ran(ace_spectral_init_host(batch, m, n, r, A.data(), B.data(), Xs.data(), st.data()))) CHECK(finite(Xs));
+        if (ran(ace_spectral_init_host(batch, m, n, r, A.data(), B.data(), Xs.data(), nullptr))) CHECK(finite(Xs));
+        const int eb = 2, d = 32;
+        auto Hm = cvec((size_t)eb * d * d);   // Hermitian: the lower triangle mirrored
+        for (int b = 0; b < eb; ++b)
+            for (int i = 0; i < d; ++i) {
+                Hm[2 * (((size_t)b * d + i) * d + i) + 1] = 0.0;
+                for (int j = 0; j < i; ++j) {
+                    Hm[2 * (((size_t)b * d + j) * d + i)] = Hm[2 * (((size_t)b * d + i) * d + j)];
+                    Hm[2 * (((size_t)b * d + j) * d + i) + 1] = -Hm[2 * (((size_t)b * d + i) * d + j) + 1];
+                }
+            }
+        const std::vector<double> tau(eb, -1e3);   // below every eigenvalue: all d pairs
+        std::vector<double> lam((size_t)eb * d), V(2 * (size_t)eb * d * d);
+        std::vector<int32_t> k(eb);
+        if (ran(ace_prox_eig_host(eb, d, 0, Hm.data(), tau.data(), lam.data(), V.data(), k.data()))) {
+            CHECK(finite(lam) && finite(V));
+            for (int v : k) CHECK(v == d);
+        }
+        const int mp = 12;
+        const auto Phi = cvec((size_t)mp * n);
+        auto b2 = magnitudes(Phi, X, batch, mp, n);
+        for (auto& v : b2) v *= v;
+        ace_phaselift_cfg c;
+        ace_phaselift_cfg_default(&c);
+        c.maxIts = 30;
+        std::vector<double> sig(2 * (size_t)batch * n), Xr(2 * (size_t)batch * mp * mp);
+        std::vector<int32_t> it(batch);
+        if (ran(ace_phaselift_solve_host(&c, batch, mp, n, Phi.data(), b2.data(), sig.data(), nullptr, nullptr))) CHECK(finite(sig));
+        if (ran(ace_phaselift_solve_host_x(&c, batch, mp, n, Phi.data(), b2.data(), sig.data(), it.data(), st.data(), Xr.data())))
+            CHECK(finite(sig) && finite(Xr));
+    }
+    // ---- InferADMM at an odd tx (solved zero-padded), the pipeline, one explicit driver sweep point
+    {
+        const int otx = 3, on = otx * rx, m = 24, ob = 2;
+        const auto A = codebook(m, on);
+        const auto H = cvec((size_t)ob * on), X0 = cvec((size_t)ob * on);
+        const auto B = magnitudes(A, H, ob, m, on);
+        ace_admm_cfg c;
+        ace_admm_cfg_default(&c);
+        c.maxiter = 10;
+        std::vector<double> Xo(2 * (size_t)ob * on), Yo(2 * (size_t)ob * m), mu(ob);
+        std::vector<int32_t> it(ob);
+        if (ran(ace_admm_solve_host(&c, ob, m, on, otx, rx, A.data(), B.data(), X0.data(), Xo.data(), Yo.data(), it.data(),
+                                    st.data(), mu.data()))) {
+            CHECK(finite(Xo) && finite(Yo) && finite(mu));
+            for (int v : it) CHECK(v >= 1 && v <= 10);
+        }
+        if (ran(ace_admm_solve_host(&c, ob, m, on, otx, rx, A.data(), B.data(), X0.data(), Xo.data(), Yo.data(), nullptr,
+                                    nullptr, nullptr)))
+            CHECK(finite(Xo) && finite(Yo));
+        const int mp = 64, mt = 60;
+        const auto Ap = codebook(mp, n);
+        const auto Bp = magnitudes(Ap, X, batch, mp, n);
+        ace_pipeline_cfg pc;
+        ace_pipeline_cfg_default(&pc, ACE_VARIANT_NUCLEAR);
+        pc.maxiter = 10;
+        std::vector<int32_t> tr(mt);
+        CHECK(ace_driver_randperm(11, 0, mp, mt, tr.data()) == 0);
+        std::vector<double> Xp(2 * (size_t)batch * n), Yp(2 * (size_t)batch * mp);
+        if (ran(ace_pipeline_solve_host(&pc, batch, mp, n, tx, rx, Ap.data(), Bp.data(), tr.data(), Xp.data(), Yp.data(), nullptr,
+                                        nullptr, nullptr)))
+            CHECK(finite(Xp));
+        const int P = 64;
+        std::vector<double> amp((size_t)P * n, 1.0 / std::sqrt((double)n)), ang((size_t)P * n), rss(P), ha(n), hg(n);
+        for (auto& a : ang) a = (double)(next_u64() & 3) * M_PI / 2;
+        for (auto& v : rss) v = -60.0 + 10.0 * uni();
+        const int32_t M1 = 25;
+        const int rc = ace_recover_driver_ex(ACE_DRIVER_A2ONLY, tx, rx, P, amp.data(), ang.data(), rss.data(), 1, 1, &M1, 10,
+                                             ha.data(), hg.data());
+        if (ran(rc == 1 ? ACE_OK : rc)) CHECK(finite(ha) && finite(hg));
+    }
+    // ---- the operator entries and the beamformer
+    {
+        const int m = 16;
+        const auto A = codebook(m, n);
+        const auto Z = cvec((size_t)batch * n), Y = cvec((size_t)batch * m);
+        const std::vector<double> mu(batch, 1.5);
+        std::vector<double> T(2 * (size_t)batch * m);
+        ace_linop_args la{};
+        la.op = ACE_LINOP_A;
+        la.path = ACE_LINOP_F64;
+        la.a_shared = 1;
+        la.batch = batch;
+        la.m = m;
+        la.n = n;
+        la.rcols = 1;
+        la.A = A.data();
+        la.Z = Z.data();
+        la.Y = Y.data();
+        la.mu = mu.data();
+        la.sentinel = -3.0;
+        la.out = T.data();
+        if (ran(ace_linop_host(&la))) CHECK(finite(T));
+        std::vector<double> C(2 * (size_t)batch * m, -3.0);
+        if (ran(ace_zgemm_host(0, 0, m, n, batch, A.data(), (long long)m * n, n, 0, Z.data(), (long long)batch * n, n, 0,
+                               C.data(), nullptr, (long long)batch * m, m, 0, 1, nullptr, 0, 0)))
+            CHECK(finite(C) && C[0] != -3.0);
+        std::vector<uint8_t> wr((size_t)batch * rx), wt((size_t)batch * tx);
+        std::vector<int32_t> bi(2 * (size_t)batch);
+        std::vector<double> rss(batch), vr(2 * (size_t)batch * rx * rx), vt(2 * (size_t)batch * tx * tx);
+        if (ran(ace_svd_beamformer_host(batch, tx, rx, X.data(), nullptr, wr.data(), wt.data(), bi.data(), rss.data(), st.data(),
+                                        vr.data(), vt.data())))
+            CHECK(finite(rss) && finite(vr) && finite(vt));
+    }
 }
 
 void gpu_solves() {
@@ -302,8 +586,9 @@ void gpu_solves() {
 }  // namespace
 
 int main(int argc, char** argv) {
-    const bool gpu = argc > 1 && strcmp(argv[1], "gpu") == 0;
+    const bool gpu = g_gpu = argc > 1 && strcmp(argv[1], "gpu") == 0;
     host_only();
+    host_entries();
     if (gpu) gpu_solves();
     if (g_fail) {
         fprintf(stderr, "%d checks failed\n", g_fail);
