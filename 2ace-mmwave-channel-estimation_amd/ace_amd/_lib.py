@@ -99,6 +99,21 @@ class GampCfg(C.Structure):
     ]
 
 
+class MinL2Cfg(C.Structure):
+    """Mirror of ``ace_minl2_cfg`` (include/ace.h)."""
+    _fields_ = [
+        ("r", C.c_int),
+        ("maxiter", C.c_int),
+        ("train_seed", C.c_int),
+        ("reserved", C.c_int),
+        ("mu0", C.c_double),
+        ("rho", C.c_double),
+        ("cc_frac", C.c_double),
+        ("tol_rel", C.c_double),
+        ("tol_abs", C.c_double),
+    ]
+
+
 _dp, _ip, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_ubyte)
 
 
@@ -193,6 +208,21 @@ def _load():
     lib.ace_gamp_solve_batch.restype = C.c_int
     lib.ace_gamp_solve_host.argtypes = [gcfgp] + [C.c_int] * 3 + [dp, dp, dp, dp, dp, ip, ip, up]
     lib.ace_gamp_solve_host.restype = C.c_int
+    mcfgp = C.POINTER(MinL2Cfg)
+    lib.ace_minl2_cfg_default.argtypes = [mcfgp]
+    lib.ace_minl2_cfg_default.restype = None
+    lib.ace_minl2_workspace_size.argtypes = [C.c_int] * 4
+    lib.ace_minl2_workspace_size.restype = C.c_size_t
+    lib.ace_minl2_admm_batch.argtypes = [mcfgp] + [C.c_int] * 5 + [vp] * 12 + [vp, C.c_size_t, vp]
+    lib.ace_minl2_admm_batch.restype = C.c_int
+    lib.ace_minl2_admm_host.argtypes = [mcfgp] + [C.c_int] * 5 + [dp, dp, dp, ip, dp, dp, dp, ip, ip, dp, dp, up]
+    lib.ace_minl2_admm_host.restype = C.c_int
+    lib.ace_minl2_solve_workspace_size.argtypes = [mcfgp] + [C.c_int] * 3
+    lib.ace_minl2_solve_workspace_size.restype = C.c_size_t
+    lib.ace_minl2_solve_batch.argtypes = [mcfgp] + [C.c_int] * 3 + [vp, vp, ip] + [vp] * 6 + [vp, C.c_size_t, vp]
+    lib.ace_minl2_solve_batch.restype = C.c_int
+    lib.ace_minl2_solve_host.argtypes = [mcfgp] + [C.c_int] * 3 + [dp, dp, ip, dp, dp, dp, ip, ip, up]
+    lib.ace_minl2_solve_host.restype = C.c_int
     lib.ace_spectral_init_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ace_spectral_init_host.restype = C.c_int
     lib.ace_path_counts.argtypes = [C.POINTER(C.c_int64), C.c_int]
@@ -250,6 +280,16 @@ def gamp_cfg(**kw) -> GampCfg:
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError(f"unknown ace_gamp_cfg field {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def minl2_cfg(**kw) -> MinL2Cfg:
+    cfg = MinL2Cfg()
+    LIB.ace_minl2_cfg_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"unknown ace_minl2_cfg field {k!r}")
         setattr(cfg, k, v)
     return cfg
 

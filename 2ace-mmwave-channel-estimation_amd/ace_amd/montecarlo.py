@@ -84,6 +84,51 @@ def vs_m(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, seed, firs
             "columns": METRICS}
 
 
+def vs_m_minl2(tx, rx, M_list, count, *, snr_db=30.0, L=3, seed, first=0, maxiter=None, device=None,
+               chunk=CHUNK) -> dict:
+    """``vs_m`` for the recovery without a prior (``minl2.infer_min_l2_batch``: ``Method.ADMM`` of Vs_M.m): the same
+    chunk grid, codebook, channels and noise draws, so the curve stands next to ``vs_m``'s.  One train partition per
+    chunk, ``engine.randperm(seed, c0, M, ceil(0.95 M))`` with c0 the chunk's first realisation: a realisation's
+    metrics are a function of (seed, M, i, chunk) alone and shards compose as ``vs_m``'s do.
+
+    Returns ``vs_m``'s keys (the status words are the evaluator's or-ed with the recovery's) plus ``r_used`` and
+    ``quality`` [nM][count] and ``stage_iters`` [nM][count][3]."""
+    import torch
+    from .engine import randperm
+    from .minl2 import infer_min_l2_batch, train_count
+    from .solver import synth_problem
+    if tx != rx:
+        raise ValueError(f"vs_m_minl2 needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    count, first, chunk = int(count), int(first), int(chunk)
+    if count < 1 or first < 0 or chunk < 1:
+        raise ValueError("count and chunk must be >= 1 and first >= 0")
+    Ms = [int(M) for M in M_list]
+    dev = torch.device("cuda" if device is None else device)
+    kw = {} if maxiter is None else {"maxiter": int(maxiter)}
+    metrics = np.empty((len(Ms), count, 4), np.float64)
+    status = np.empty((len(Ms), count), np.uint32)
+    r_used = np.empty((len(Ms), count), np.int32)
+    quality = np.empty((len(Ms), count), np.float64)
+    stage_iters = np.empty((len(Ms), count, 3), np.int32)
+    end = first + count
+    for k, M in enumerate(Ms):
+        mt = train_count(M)
+        for c0 in range(first // chunk * chunk, end, chunk):
+            A, B, _, H = synth_problem(seed, c0, chunk, M, tx, rx, L=L, snr_db=snr_db, device=dev)
+            rec = infer_min_l2_batch(A, B, randperm(seed, c0, M, mt), **kw)
+            ev = evaluate_batch(rec.X, H, tx, rx)
+            lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+            rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
+            metrics[k, rows] = ev.metrics[sel].cpu().numpy()
+            status[k, rows] = (ev.status[sel] | rec.status[sel]).cpu().numpy().view(np.uint32)
+            r_used[k, rows] = rec.r_used[sel].cpu().numpy()
+            quality[k, rows] = rec.quality[sel].cpu().numpy()
+            stage_iters[k, rows] = rec.stage_iters[sel].cpu().numpy()
+    return {"M": np.asarray(Ms, np.int64), "metrics": metrics, "status": status,
+            "mean": metrics.mean(axis=1), "n_degenerate": ((status & ACE_ST_EVAL_DEGENERATE) != 0).sum(axis=1),
+            "columns": METRICS, "r_used": r_used, "quality": quality, "stage_iters": stage_iters}
+
+
 SPARSE = ("plomp", "plomp_2s", "perfect_cs")
 SPARSE_GAMP = ("plgamp", "perfect_cs_gamp")
 

@@ -662,6 +662,102 @@ int ace_gamp_solve_host(const ace_gamp_cfg* cfg, int batch, int d, int N, const 
                         double* xhat, double* xvar, double* params, int32_t* em_iters, int32_t* trace,
                         uint32_t* status);   /* host arrays; allocates, copies, synchronous */
 
+/* ---- batched min-L2 ADMM (Method.ADMM of Vs_M.m: ADMM_v2(..., version 0) -> inferMinL2.m) ------------------
+ * InferADMM of ADMM_v2/inferMinL2.m:229-326 with lambda = 0 (the only value a caller passes), restated for a batch
+ * of realisations against one shared A: the 2ACE iteration without the low-rank Z-block,
+ *   X = pinv(A) (Y - M / mu),  Y = ArgMinY(A X, B, M, mu),  M += mu (A X - Y),
+ * with the best-objective iterate, the residuals and thresholds of :304-310 (sqrt(m r), sqrt(n r), sqrt(2 m r)), the
+ * stop test and mu *= rho while the combined residual is above 0.9 of the last one.  One launch runs the
+ * initialisation (:244-257) and every iteration of one call for the whole batch (csrc/ace_minl2.hip); the three
+ * m x n products of an iteration run on the f64 matrix cores.
+ * ace_minl2_admm_batch: one InferADMM call.  A [m][n] c128 row-major, B [batch][m] f64, X0 [batch][r][n] c128
+ * (column j of realisation b at X0[b][j][:]), rcols [batch] int32 or NULL: the columns of realisation b that exist
+ * (clipped to 1 .. r; NULL: r for all) -- columns at and beyond rcols[b] are never read and never influence a result;
+ * scale_by_row 1: the row form (the r columns share the row norm; X [batch][r][n] and Y [batch][r][m] return all
+ * columns, zeros beyond rcols[b]), 0: the per-column form (X [batch][n], Y [batch][m]: the column with the smallest
+ * objective, first index, NaN skipped as MATLAB's min does).  All DEVICE.  Further outputs, each may be NULL: Xall
+ * [batch][r][n], every column of the iterate at the best iteration; iters [batch] int32, the iterations run; objcol
+ * [batch] int32, the column returned (0 in the row form); opt_obj [batch] f64, the best objective || |A X| - B ||; mu
+ * [batch] f64 at exit; status [batch]: ACE_ST_CONVERGED when the stop test passed, ACE_ST_NO_OPT when no objective was
+ * ever finite (the last iterate is returned; the reference would raise).
+ * workspace: ace_minl2_workspace_size(batch, m, n, r) bytes of DEVICE memory (pinv(A), the Gram matrix and its
+ * Cholesky factor, and 16 (5 m + 4 n) 32 B of state per work-group: one per realisation with r > 1, one per 32
+ * realisations with r = 1); ACE_ERR_WORKSPACE when NULL or shorter.  Synchronises the stream once (the pivot test of
+ * the setup), then asynchronous; no allocation, no atomics.  A realisation's outputs are a function of its own B, X0
+ * and rcols entry, A, the sizes and cfg alone.
+ * cfg: r, cc_frac and train_seed belong to the whole recovery (inferMinL2); a stage reads maxiter, mu0, rho, tol_rel
+ * and tol_abs.
+ * Limits: 1 <= n <= 1024, 1 <= m <= 4096, 1 <= r <= 32, batch >= 1, maxiter >= 1, mu0 and rho positive, tolerances
+ * not negative; a NULL cfg, A, B, X0, X or Y and a value outside these return ACE_ERR_ARG before any HIP call.
+ * ace_minl2_workspace_size returns 0 for sizes outside the limits.
+ * Departures from the reference:
+ *   - pinv(A) is formed through the Cholesky factor of A^H A (m > n) or A A^H; a pivot at rounding level of its
+ *     diagonal entry (rank-deficient A) returns ACE_ERR_UNSUPPORTED where MATLAB's pinv would truncate the singular
+ *     value -- the contract ace_phaselift_solve_batch has for m <= n;
+ *   - m <= n: A pinv(A) = I is used exactly (A X is Y - M / mu itself, not the rounded product), so the stage stops
+ *     after one iteration with an objective at rounding level, as the reference does up to its rounding;
+ *   - m <= n, per-column form: every column's objective is at rounding level, so which column is "best" is decided by
+ *     rounding noise, here as in the reference (two float64 runs of the reference differ in it).
+ *
+ * ace_minl2_solve_batch: the whole of inferMinL2.  A /= ||A||_F / sqrt(m), B /= ||B|| (the tol_abs guards);
+ * r = min(cfg->r, m, n); m_t = ceil(m cc_frac) train rows (ceil: inferLowRankV4 takes floor); on the train rows the
+ * spectral initialisation, the column count of :187-190 per realisation (r_b = max(first k with 90 % of the
+ * spectrum's sum, 3) where the r leading eigenvalues hold 90 %, then min(r_b, m_t, n): with r < 3 that can be MORE
+ * than r, and min(max(r, 3), m_t, n) columns are initialised for it; the copy of that block at :203-206 changes
+ * nothing), the row-form stage, X <- X eig(X^H X) (ascending, not re-sorted) and the per-column
+ * stage; the quality 1 - || |A_te x| - B_te || / ||B_te|| on the test rows; where it exceeds 0.6 a row-form r = 1
+ * stage on the full A from that x, rolled back at similarity < 0.6 (ACE_ST_ROLLBACK); X and Y scaled by
+ * ||B|| / ||A||.  Without test rows (m < 20) the quality is NaN and there is no refinement, as in the reference.
+ * train_idx: HOST array [m_t] of 0-based rows, ONE partition for the batch (the test rows are the sorted complement);
+ * NULL draws it from the build's counter RNG (ace_driver_randperm(train_seed, 0, m, m_t)).
+ * Outputs (DEVICE): X [batch][n], Y [batch][m] c128 (without refinement, or after a rollback, Y lives on the train
+ * rows: its first m_t entries in train order, zeros beyond); may be NULL: quality [batch] f64, stage_iters [batch][3]
+ * int32 (row stage, per-column stage, refinement; 0 where not run), r_used [batch] int32, status [batch]:
+ * ACE_ST_CONVERGED (the stop test of the last stage the realisation ran), ACE_ST_NO_OPT (any stage),
+ * ACE_ST_ROLLBACK, ACE_ST_EIG_NOCONV (the spectral initialisation or the rotation).
+ * workspace: ace_minl2_solve_workspace_size(cfg, batch, m, n) bytes of DEVICE memory (0 outside the limits).
+ * Realisations are solved in groups of equal column count, and the refinement on those that take it; a
+ * realisation's outputs do not depend on the grouping.  NOT asynchronous: the host decides the groups and the
+ * refinement set, so the call synchronises the stream at every host round trip -- the upload of the row table, the
+ * read-back of the column counts, the upload of the groups' indices, the pivot test of each of the two pinv setups, the
+ * read-back of the qualities and the upload of the refinement set (each upload waits before and after its copy) -- and
+ * only the last launches (the refinement stage, the rollback and the rescaling) are still in flight when it returns.
+ * Further departures:
+ *   - per-realisation partitions are not supported: the per-realisation machinery of ace_pipeline_solve_batch is
+ *     built around (I + K)^-1 and does not carry over.  Each realisation's marginal distribution is unchanged (the
+ *     channels are independent of the partition);
+ *   - a rank-deficient A_t, or A where a refinement runs, returns ACE_ERR_UNSUPPORTED;
+ *   - the spectrum's sum is taken as the trace (the sum of B_i^2 over the nonzero rows of A_t) and the leading
+ *     eigenvalues as the squared norms of the initialisation's columns. */
+typedef struct ace_minl2_cfg {
+    int r;             /* 20 (inferMinL2.m:3): the column count of the whole recovery before its 0.9-energy rule */
+    int maxiter;       /* 500, every stage */
+    int train_seed;    /* seed of the partition draw of the whole recovery */
+    int reserved;
+    double mu0;        /* 1e-3 (:260) */
+    double rho;        /* 1.03 (:261) */
+    double cc_frac;    /* 0.95 (:34; m_t = ceil(m cc_frac)) */
+    double tol_rel;    /* 1e-4 */
+    double tol_abs;    /* 1e-8 */
+} ace_minl2_cfg;
+void ace_minl2_cfg_default(ace_minl2_cfg* cfg);
+size_t ace_minl2_workspace_size(int batch, int m, int n, int r);
+int ace_minl2_admm_batch(const ace_minl2_cfg* cfg, int batch, int m, int n, int r, int scale_by_row, const double* A,
+                         const double* B, const double* X0, const int32_t* rcols, double* X, double* Y, double* Xall,
+                         int32_t* iters, int32_t* objcol, double* opt_obj, double* mu, uint32_t* status,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int ace_minl2_admm_host(const ace_minl2_cfg* cfg, int batch, int m, int n, int r, int scale_by_row, const double* A,
+                        const double* B, const double* X0, const int32_t* rcols, double* X, double* Y, double* Xall,
+                        int32_t* iters, int32_t* objcol, double* opt_obj, double* mu,
+                        uint32_t* status);   /* host arrays; allocates, copies, synchronous */
+size_t ace_minl2_solve_workspace_size(const ace_minl2_cfg* cfg, int batch, int m, int n);
+int ace_minl2_solve_batch(const ace_minl2_cfg* cfg, int batch, int m, int n, const double* A, const double* B,
+                          const int32_t* train_idx_host, double* X, double* Y, double* quality, int32_t* stage_iters,
+                          int32_t* r_used, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int ace_minl2_solve_host(const ace_minl2_cfg* cfg, int batch, int m, int n, const double* A, const double* B,
+                         const int32_t* train_idx, double* X, double* Y, double* quality, int32_t* stage_iters,
+                         int32_t* r_used, uint32_t* status);   /* host arrays; allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
@@ -732,7 +828,7 @@ int ace_path_counts(int64_t* counts, int reset);
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
  * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used),
- * "omp", "gamp" (m = d, the atoms' length).  With the kernel's static LDS
+ * "omp", "gamp" (m = d, the atoms' length), "minl2" (m = the measurement count; 0 at every m).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
 int ace_lds_request(const char* kernel, int m, size_t* bytes);
