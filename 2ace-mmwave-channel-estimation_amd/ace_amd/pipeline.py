@@ -258,11 +258,12 @@ def infer_low_rank_pipeline_batch(A, B, tx, rx, train_idx, *, variant="A2only", 
     return out
 
 
-def SpectralInitialize(A, B, r):
+def SpectralInitialize(A, B, r, return_status=False):
     """X = SpectralInitialize(A, B, r) (inferLowRankV4_multi.m:561-574) on the GPU, the kernels of
     the pipeline's own initialisation.  A: [m, n] complex; B: [m] or [batch, m] magnitudes.
     Returns [n, r] (or [batch, n, r]) complex128: column k = sqrt(s_k) v_k, eigenvectors up to a
-    unit phase each."""
+    unit phase each; with return_status also the realisations' ACE_ST_* bits (uint32, ACE_ST_EIG_NOCONV from
+    the eigensolver)."""
     A = np.ascontiguousarray(A, dtype=np.complex128)
     B = np.asarray(B, dtype=np.float64)
     single = B.ndim == 1
@@ -276,5 +277,7 @@ def SpectralInitialize(A, B, r):
     check(LIB.ace_spectral_init_host(batch, m, n, int(r), A.ctypes.data, Bb.ctypes.data, X.ctypes.data,
                                      st.ctypes.data))
     X = np.transpose(X, (0, 2, 1))
+    if return_status:
+        return (X[0], st[0]) if single else (X, st)
     return X[0] if single else X
 

@@ -972,7 +972,25 @@ __global__ __launch_bounds__(256) void trieig_kernel(int mt, const double* tau_p
             at(2, mt - 1) = cur_du;
             at(3, mt - 1) = 0.0;
             at(4, mt - 1) = 0.0;
-            for (int i = 0; i < mt; ++i) at(5, i) = 1.0 + 0.01 * sin(1.0 + 0.7 * i + 1.3 * q);  // start vector
+            // start vector.  1 + 0.01 sin(.) spans only {1, sin, cos} across q: where T splits and the eigenvalue
+            // is exactly multiple, a solve scales the cluster's rows alike, so a fourth member's start lies in the
+            // span of the first three, the projection leaves rounding noise, and what the second solve amplifies
+            // is noise against the neighbouring eigenvectors' 1 / gap^2 (measured: 8e-11 of a neighbour in the
+            // 16th vector of a 16-fold diagonal entry, d = 256).  From the fourth member on the start is a hash of
+            // (i, q - q0), uniform in [-1, 1) as LAPACK dstein's dlarnv start; the first three keep their values.
+            if (q - q0 < 3) {
+                for (int i = 0; i < mt; ++i) at(5, i) = 1.0 + 0.01 * sin(1.0 + 0.7 * i + 1.3 * q);
+            } else {
+                for (int i = 0; i < mt; ++i) {
+                    unsigned h = (unsigned)i * 2654435761u ^ (unsigned)(q - q0) * 0x9E3779B9u;
+                    h ^= h >> 15;
+                    h *= 0x2C1B3C6Du;
+                    h ^= h >> 12;
+                    h *= 0x297A2D39u;
+                    h ^= h >> 15;
+                    at(5, i) = (double)h * 4.656612873077393e-10 - 1.0;   // h 2^-31 - 1
+                }
+            }
             double* zq = Z + (long long)q * mt;
             // The solves below walk the lane's LU arrays (lane-interleaved global scratch) one row after the
             // other; the loads of a block of TE_PF rows are issued together ahead of the block's dependent
