@@ -20,12 +20,14 @@ from .rss import evaluate_rss_host, evaluate_rss_batch, dbm_to_amp, RssEval  # n
 from .scan import beam_scan_host, beam_scan_batch, ScanResult  # noqa: F401
 from .omp import omp_host, omp_batch, OmpResult  # noqa: F401
 from .gamp import embgamp_host, embgamp_batch, GampResult  # noqa: F401
+from .prgamp import prgamp_host, prgamp_batch, prgamp_draws, PrGampResult  # noqa: F401
 from .minl2 import (minl2_admm_host, minl2_admm_batch, infer_min_l2_host, infer_min_l2_batch, inferMinL2,  # noqa: F401
                     MinL2Stage, MinL2Result)
 from ._lib import MinL2Cfg, minl2_cfg  # noqa: F401
 from ._lib import ACE_ST_EVAL_DEGENERATE, ACE_ST_OMP_DEPENDENT  # noqa: F401
 from ._lib import ACE_ST_GAMP_NANBREAK, ACE_ST_GAMP_MAXEM, ACE_ST_GAMP_FAILED, GampCfg, gamp_cfg  # noqa: F401
-from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular, omp, gamp, sparse, minl2  # noqa: F401
+from ._lib import ACE_ST_PRGAMP_FAILED, ACE_ST_PRGAMP_MAXTRY, PrGampCfg, prgamp_cfg  # noqa: F401
+from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular, omp, gamp, prgamp, sparse, minl2  # noqa: F401
 from . import stages  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

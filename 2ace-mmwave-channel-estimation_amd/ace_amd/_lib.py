@@ -32,6 +32,8 @@ ACE_ST_OMP_DEPENDENT = 1024
 ACE_ST_GAMP_NANBREAK = 2048
 ACE_ST_GAMP_MAXEM = 4096
 ACE_ST_GAMP_FAILED = 8192
+ACE_ST_PRGAMP_FAILED = 16384
+ACE_ST_PRGAMP_MAXTRY = 32768
 
 ACE_TRAIN_SHARED = 0
 ACE_TRAIN_PER_REALISATION = 1
@@ -96,6 +98,19 @@ class GampCfg(C.Structure):
         ("reserved", C.c_int),
         ("step0", C.c_double),
         ("gamp_tol", C.c_double),
+    ]
+
+
+class PrGampCfg(C.Structure):
+    """Mirror of ``ace_prgamp_cfg`` (include/ace.h)."""
+    _fields_ = [
+        ("sparse_rat", C.c_double),
+        ("snr_db_init", C.c_double),
+        ("snr_db", C.c_double),
+        ("max_try", C.c_int),
+        ("nit_em", C.c_int),
+        ("gamp_nit", C.c_int),
+        ("reserved", C.c_int),
     ]
 
 
@@ -208,6 +223,15 @@ def _load():
     lib.ace_gamp_solve_batch.restype = C.c_int
     lib.ace_gamp_solve_host.argtypes = [gcfgp] + [C.c_int] * 3 + [dp, dp, dp, dp, dp, ip, ip, up]
     lib.ace_gamp_solve_host.restype = C.c_int
+    pcp = C.POINTER(PrGampCfg)
+    lib.ace_prgamp_cfg_default.argtypes = [pcp]
+    lib.ace_prgamp_cfg_default.restype = None
+    lib.ace_prgamp_workspace_size.argtypes = [C.c_int] * 4
+    lib.ace_prgamp_workspace_size.restype = C.c_size_t
+    lib.ace_prgamp_solve_batch.argtypes = [pcp] + [C.c_int] * 3 + [vp] * 10 + [C.c_size_t, vp]
+    lib.ace_prgamp_solve_batch.restype = C.c_int
+    lib.ace_prgamp_solve_host.argtypes = [pcp] + [C.c_int] * 3 + [dp, dp, dp, dp, dp, ip, up, ip, dp]
+    lib.ace_prgamp_solve_host.restype = C.c_int
     mcfgp = C.POINTER(MinL2Cfg)
     lib.ace_minl2_cfg_default.argtypes = [mcfgp]
     lib.ace_minl2_cfg_default.restype = None
@@ -280,6 +304,16 @@ def gamp_cfg(**kw) -> GampCfg:
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError(f"unknown ace_gamp_cfg field {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def prgamp_cfg(**kw) -> PrGampCfg:
+    cfg = PrGampCfg()
+    LIB.ace_prgamp_cfg_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"unknown ace_prgamp_cfg field {k!r}")
         setattr(cfg, k, v)
     return cfg
 

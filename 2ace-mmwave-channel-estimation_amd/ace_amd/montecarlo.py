@@ -131,10 +131,11 @@ def vs_m_minl2(tx, rx, M_list, count, *, snr_db=30.0, L=3, seed, first=0, maxite
 
 SPARSE = ("plomp", "plomp_2s", "perfect_cs")
 SPARSE_GAMP = ("plgamp", "perfect_cs_gamp")
+SPARSE_PRGAMP = ("prgamp",)
 
 
 def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=0, pl_maxits=4000, tol=1e-12,
-                device=None, chunk=CHUNK, gamp=False) -> dict:
+                device=None, chunk=CHUNK, gamp=False, prgamp=False, max_try=100) -> dict:
     """The sparse recoveries of ``sparse.py`` on ``vs_m``'s sweep: the same chunk grid, codebook, channels and noise
     draws (``synth_problem`` at (seed, M, realisation index)), so the curves stand next to ``vs_m``'s.  Per M and
     realisation, the four ``evaluate_batch`` columns ([nM][count][4] each, keys ``SPARSE``) of
@@ -156,6 +157,19 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
 
     with ``status_<key>`` (the evaluator's bits or-ed with the GAMP stage's) and ``em_iters_<key>`` [nM][count].
 
+    ``prgamp=True`` adds the direct compressive phase retrieval ``Method.PRGAMP`` (key ``SPARSE_PRGAMP``; every other
+    key and value is unchanged):
+
+      * ``prgamp`` -- ``prgamp.prgamp_batch`` on Phi = A AD and the magnitude measurements at the synth's own scale
+                      (MyCPR.m:110-120: sparse_rat = s / n with n the dictionary size, SNRdBinit 20, SNRdB 25, nitEM
+                      50), scored like ``plomp``, where M <= 256; NaN beyond (the kernel's row limit).  The restart
+                      draws come from the counter generator at (seed, realisation index), so shards compose.
+
+    with ``status_prgamp`` (the evaluator's bits or-ed with the solver's) and ``tries_prgamp`` [nM][count] (numTry).
+    ``max_try``: the restarts per realisation, default the reference's 100.  The draws cost 16 chunk max_try Qt Qr bytes
+    per sweep point: 105 MB at the default chunk of 64, a 32 x 32 dictionary and 100 tries (1.7 GB at a 16384-atom
+    dictionary), and a realisation that never reaches the stop level runs all of them.
+
     ``s``: the sparsity handed to both (default L, what Vs_M.m passes).  Also returned: ``mCS`` [nM], the status
     words of the three evaluations or-ed with the OMP stage's (``status_<key>``), the OMP stage's counts (``count_<key>``),
     ``gain_percsi_ana`` [nM][count] (``evaluate_batch(H, H)``: the H scored is ``vs_m``'s) and the means.  Only
@@ -167,6 +181,7 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     full 16 x 16 curve tens of minutes; lower ``pl_maxits`` to bound it and say so next to the numbers."""
     import torch
     from . import sparse, synth
+    from . import prgamp as prgamp_mod
     from .solver import synth_problem
     if tx != rx:
         raise ValueError(f"vs_m_sparse needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
@@ -186,6 +201,10 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     out.update({k: np.full((len(Ms), count, 4), np.nan) for k in keys_g})
     stat.update({k: np.zeros((len(Ms), count), np.uint32) for k in keys_g})
     emi = {k: np.zeros((len(Ms), count), np.int32) for k in keys_g}
+    keys_p = SPARSE_PRGAMP if prgamp else ()
+    out.update({k: np.full((len(Ms), count, 4), np.nan) for k in keys_p})
+    stat.update({k: np.zeros((len(Ms), count), np.uint32) for k in keys_p})
+    tries = {k: np.zeros((len(Ms), count), np.int32) for k in keys_p}
     noise_power = 10.0 ** (-snr_db / 10.0)
     percsi = np.empty((len(Ms), count), np.float64)
     mcs = np.empty(len(Ms), np.int64)
@@ -215,6 +234,9 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
                                                                      noise_power=noise_power)
             if gamp:
                 res["plgamp"] = sparse._gamp_stage2(ts, sig, s, noise_power, Phi.shape[1])
+            if prgamp and M <= prgamp_mod.M_MAX:
+                res["prgamp"] = prgamp_mod.prgamp_batch(Phi, Braw.contiguous(), s / Phi.shape[1], seed=seed, first=c0,
+                                                        max_try=int(max_try))
             lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
             rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
             percsi[k, rows] = evaluate_batch(H, H, tx, rx).gain_ana[sel].cpu().numpy()
@@ -223,13 +245,15 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
                 out[name][k, rows] = ev.metrics[sel].cpu().numpy()
                 # the evaluator's bits and the OMP stage's (ACE_ST_EVAL_DEGENERATE there: a non-finite PhaseLift output)
                 stat[name][k, rows] = (ev.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
-                if name in emi:
+                if name in tries:
+                    tries[name][k, rows] = r.counts[sel, 0].cpu().numpy()
+                elif name in emi:
                     emi[name][k, rows] = r.em_iters[sel].cpu().numpy()
                 else:
                     cnt[name][k, rows] = r.count[sel].cpu().numpy()
     return {"M": np.asarray(Ms, np.int64), "mCS": mcs, "s": s, **out, "columns": METRICS, "gain_percsi_ana": percsi,
             **{f"status_{k}": v for k, v in stat.items()}, **{f"count_{k}": v for k, v in cnt.items()},
-            **{f"em_iters_{k}": v for k, v in emi.items()}, "mean": {k: v.mean(axis=1) for k, v in out.items()}}
+            **{f"em_iters_{k}": v for k, v in emi.items()}, **{f"tries_{k}": v for k, v in tries.items()}, "mean": {k: v.mean(axis=1) for k, v in out.items()}}
 
 
 BASELINES = ("gain_percsi_ana", "gain_percsi_dig", "aoda_err_est", "gain_est_aoda", "gain_sweep", "aoda_err_sweep")

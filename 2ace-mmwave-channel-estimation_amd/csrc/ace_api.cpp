@@ -108,6 +108,7 @@ int ace_lds_request(const char* kernel, int m, size_t* bytes) {
     else if (k == "scan") *bytes = scan_request_bytes();
     else if (k == "omp") *bytes = omp_request_bytes(m);
     else if (k == "gamp") *bytes = gamp_request_bytes(m);
+    else if (k == "prgamp") *bytes = prgamp_request_bytes(m);
     else if (k == "minl2") *bytes = minl2_request_bytes(m);
     else if (k == "part_geinv") *bytes = part_geinv_request_bytes(m);
     else return fail(ACE_ERR_ARG, "unknown kernel '%s'", kernel);

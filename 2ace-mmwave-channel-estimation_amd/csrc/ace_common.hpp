@@ -288,6 +288,7 @@ size_t heev2_request_bytes(int d, int which);   // ... of he2hb_kernel (0), hb2s
 size_t scan_request_bytes();                 // ... of scan_kernel (the same at every shape)
 size_t omp_request_bytes(int d);             // ... of omp_kernel at atom length d
 size_t gamp_request_bytes(int d);            // ... of gamp_kernel at atom length d
+size_t prgamp_request_bytes(int m);          // ... of prgamp_kernel at m measurements
 size_t minl2_request_bytes(int m);           // ... of minl2_kernel at m measurements (none)
 size_t part_geinv_request_bytes(int te);     // ... of part_geinv_kernel at te test rows
 

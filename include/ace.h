@@ -662,6 +662,67 @@ int ace_gamp_solve_host(const ace_gamp_cfg* cfg, int batch, int d, int N, const 
                         double* xhat, double* xvar, double* params, int32_t* em_iters, int32_t* trace,
                         uint32_t* status);   /* host arrays; allocates, copies, synchronous */
 
+/* ---- batched PR-GAMP (Method.PRGAMP of Vs_M.m: MyCPR.m:110-120 -> MyPRGAMP.m:71 -> prGAMP4) --------------
+ * prGAMP4(abs_y, D, opt_pr) of the reference's vendored GAMP package (3rd_software_component/GAMP/trunk/code:
+ * phase/prGAMP4.m, phase/ncCAwgnEstimOut.m, main/gampEst.m, main/estimInvert.m, main/CAwgnEstimIn.m,
+ * main/SparseScaEstim.m, main/GampOpt.m), restated for a batch of independent realisations (T = 1 column each)
+ * against one shared matrix: compressive phase retrieval straight from the magnitudes |D x + w|, without the PhaseLift
+ * compression stage.  Generalised approximate message passing under the non-coherent output channel (a Bessel ratio in
+ * the posterior, the Bethe cost with its fixed-point inversion for the adaptive step, variance normalisation, a damped
+ * pvar, a window of passed utilities), inside an EM loop that learns the noise variance and tunes the
+ * Bernoulli-Gaussian prior, inside random restarts.  One launch runs every try, every EM iteration and every GAMP
+ * iteration (csrc/ace_prgamp.hip states the iteration, the fixed options and the reference's quirks it keeps).
+ * cfg: the MyCPR.m set is ace_prgamp_cfg_default with sparse_rat = s / n.  gamp_nit, nit_em and max_try may be set
+ * small (8, 0, 1: one short cold GAMP call, the kernel-level tests' handle).
+ * D [m][N] c128 row-major, Y [batch][m] f64 (the magnitudes; MyPRGAMP passes sqrt of the squared measurements; the
+ * absolute value is taken), G [batch][max_try][N] c128: the restart draws, standing for randn(nx, 2) * [1; 1i] of
+ * prGAMP4.m:608 (real and imaginary parts of unit variance; MATLAB's stream cannot be reproduced, so they are the
+ * caller's) -- 16 batch max_try N bytes, 26.8 GB at batch 4096, N 4096 and the reference's 100 tries: a caller
+ * sweeping many realisations at the full try count goes in chunks.  All DEVICE.
+ * Outputs: xhat [batch][N] c128, the best try's estimate; info [batch][8] f64 = the best residual
+ * 20 log10(|| |D xhat| - y || / ||y||) in dB, the noise variance wvar_hat of the best try's last EM iteration,
+ * sparseRat_hat, xvar0_hat (both of the LAST try, as out.sparseRat_hat / out.xvar0_hat are), xmean0sq_hat (0: the
+ * mean is not tuned), SNRdB_est of the best try's last EM iteration, two reserved zeros; counts [batch][4] int32 =
+ * numTry, the best try (1-based), the EM iterations of the best try, support_size (-1 where the reference leaves it
+ * NaN: no try reached the stop level); status [batch] (may be NULL); trace (may be NULL) [batch][max_try][nit_em + 1][2]
+ * int32, per gampEst call its iterations and its passed iterations, 0 for calls that did not run; vals (may be NULL)
+ * [batch][max_try][nit_em + 1] f64, the last passed utility of each call.
+ * workspace: ace_prgamp_workspace_size(batch, m, N, max_try) bytes of DEVICE memory (the N-long and m-long state
+ * vectors: 184 B per atom and 192 B per row, per realisation rounded up to 16); ACE_ERR_WORKSPACE when NULL or
+ * shorter.  Asynchronous on stream; no allocation, no host synchronisation, no atomics.  A realisation's outputs are a
+ * function of (y_b, G_b, D, cfg, m, N) alone.
+ * Limits: 1 <= m <= 256, 1 <= N <= 16384, batch >= 1, 0 < sparse_rat <= 1, snr_db and snr_db_init finite (capped at
+ * 100), max_try >= 1, nit_em >= 0, gamp_nit >= 1; a NULL cfg, D, Y, G, xhat, info or counts and a value outside these
+ * return ACE_ERR_ARG, m > 256 or N > 16384 or a refused dynamic LDS request ACE_ERR_UNSUPPORTED, all before any HIP
+ * call.  ace_prgamp_workspace_size returns 0 for sizes outside the limits.
+ * Status:
+ *   ACE_ST_PRGAMP_FAILED  the reference would raise and MyPRGAMP's catch returns zeros: xhat and info are zeroed.
+ *                         Reachable: CAwgnEstimIn's assert(var0 > 0) on xvar0 (y = 0) or on a tuned var0 that is NaN
+ *                         or <= 0; estFin_best never assigned because every try ended with a NaN or Inf residual
+ *                         (a y whose squared norm overflows ends there and is failed at once);
+ *   ACE_ST_PRGAMP_MAXTRY  the tries ran out above the stop level -(snr_db + 2) dB: xhat is the best try, as in the
+ *                         reference;
+ *   ACE_ST_EVAL_DEGENERATE  a non-finite entry of y_b: zeros. */
+#define ACE_ST_PRGAMP_FAILED 16384u
+#define ACE_ST_PRGAMP_MAXTRY 32768u
+typedef struct ace_prgamp_cfg {
+    double sparse_rat;    /* opt_pr.sparseRat: s / n (the kernel applies tuneOn's min(., 0.9)) */
+    double snr_db_init;   /* opt_pr.SNRdBinit (20): the first noise variance mean(y^2) / (1 + 10^(./10)) */
+    double snr_db;        /* opt_pr.SNRdB (25): xvar0 and the stop level -(SNRdB + 2) dB */
+    int max_try;          /* opt_pr.maxTry (100) */
+    int nit_em;           /* opt_pr.nitEM (50): up to nit_em + 1 gampEst calls per try */
+    int gamp_nit;         /* opt_gamp_init.nit (200) */
+    int reserved;
+} ace_prgamp_cfg;
+void ace_prgamp_cfg_default(ace_prgamp_cfg* cfg);   /* the MyCPR.m set; sparse_rat 0 (the caller's to set) */
+size_t ace_prgamp_workspace_size(int batch, int m, int N, int max_try);
+int ace_prgamp_solve_batch(const ace_prgamp_cfg* cfg, int batch, int m, int N, const double* D, const double* Y,
+                           const double* G, double* xhat, double* info, int32_t* counts, uint32_t* status,
+                           int32_t* trace, double* vals, void* workspace, size_t workspace_bytes, void* stream);
+int ace_prgamp_solve_host(const ace_prgamp_cfg* cfg, int batch, int m, int N, const double* D, const double* Y,
+                          const double* G, double* xhat, double* info, int32_t* counts, uint32_t* status,
+                          int32_t* trace, double* vals);   /* host arrays; allocates, copies, synchronous */
+
 /* ---- batched min-L2 ADMM (Method.ADMM of Vs_M.m: ADMM_v2(..., version 0) -> inferMinL2.m) ------------------
  * InferADMM of ADMM_v2/inferMinL2.m:229-326 with lambda = 0 (the only value a caller passes), restated for a batch
  * of realisations against one shared A: the 2ACE iteration without the low-rank Z-block,
@@ -828,7 +889,7 @@ int ace_path_counts(int64_t* counts, int reset);
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
  * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used),
- * "omp", "gamp" (m = d, the atoms' length), "minl2" (m = the measurement count; 0 at every m).  With the kernel's static LDS
+ * "omp", "gamp" (m = d, the atoms' length), "prgamp" (m = the measurement count), "minl2" (m = the measurement count; 0 at every m).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
 int ace_lds_request(const char* kernel, int m, size_t* bytes);
