@@ -147,6 +147,18 @@ class StageArgs(C.Structure):
                 + [("iout", _ip), ("flags_out", _ip), ("bout", _bp)])
 
 
+class NmsArgs(C.Structure):
+    """Mirror of ``ace_nms_args`` (include/ace.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("op", "batch", "n", "m", "it", "fixed_iters", "guard", "done_count")]
+                + [(k, C.c_double) for k in ("tol_rel", "tol_abs", "rho", "sentinel")]
+                + [(k, _dp) for k in ("Xinit", "P0", "G", "K", "B", "Yo", "Yn", "M", "Eo", "AEo", "optW", "optY",
+                                      "curW", "state")]
+                + [("flags", _ip)]
+                + [(k, _dp) for k in ("B_out", "Yo_out", "Yn_out", "M_out", "Eo_out", "En_out", "AEo_out", "AEn_out",
+                                      "optW_out", "optY_out", "curW_out", "V", "Wsel", "state_out")]
+                + [(k, _ip) for k in ("flags_out", "done_count_out", "guard_ok")])
+
+
 def _load():
     if not LIB_PATH.exists():
         raise ImportError(
@@ -255,6 +267,8 @@ def _load():
     lib.ace_lds_request.restype = C.c_int
     lib.ace_stage_host.argtypes = [C.POINTER(StageArgs)]
     lib.ace_stage_host.restype = C.c_int
+    lib.ace_nms_host.argtypes = [C.POINTER(NmsArgs)]
+    lib.ace_nms_host.restype = C.c_int
     lib.ace_last_error.argtypes = []
     lib.ace_last_error.restype = C.c_char_p
     lib.ace_version.argtypes = []

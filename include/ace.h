@@ -38,6 +38,8 @@
  *                            them (init :296-310, ArgMinY :511-533, opt_X / opt_Y :384-385, the
  *                            rotation :263-264, quality :68, best of restarts :79-83, rollback and
  *                            rescale :93-107, the per-realisation partitions' Schur form) on host arrays.
+ *  ace_nms_host           <- test entry: one operation of the A2nuclear m-space iteration (init, one
+ *                            iteration, the pending convergence tests, the output parts) on host arrays.
  *
  * Conventions
  *  - Complex values are complex128, interleaved (re, im) doubles.
@@ -340,8 +342,9 @@ int ace_zgemm_host(int mode, int conj_l, int M, int K, int nb, const double* L, 
  *   tkcnt [2]: top-K tridiagonal uses and fallbacks to the Jacobi eigensolver
  * ACE_ERR_ARG: bad shapes or missing arrays; ACE_ERR_UNSUPPORTED: a combination no solve makes (wmode without
  * pingpong or at r > 1 or in the init form, pingpong without wmode, lean outside its conditions, odd tx).  The
- * producers of the Z-step's inputs that carry solver state (the fused apply_AH, the m-space steady state, the
- * compact launch and the lazy dual residual) are not reachable from here.
+ * producers of the Z-step's inputs that carry solver state (the fused apply_AH, the A2only m-space steady state
+ * and the compact launch) are not reachable from here; the A2nuclear m-space state and its lazy dual residual
+ * are reachable through ace_nms_host below.
  * Synchronous; allocates its own device memory. */
 #define ACE_ZP_NIN 15
 #define ACE_ZP_NFLAG 4
@@ -427,6 +430,48 @@ typedef struct ace_stage_args {
     unsigned char* bout;
 } ace_stage_args;
 int ace_stage_host(const ace_stage_args* args);
+
+/* ---- test entry: one operation of the A2nuclear m-space iteration (csrc/ace_nucmsp.hip) on host arrays --------
+ * The benchmarked inner loop of the A2nuclear r = 1 solve on its own (tests/test_gpu_nms.py compares it with the
+ * references of tests/nms_ref.py).  The entry fills the kernel's argument blocks and one control block per
+ * realisation the way the solve does (lazy dual residual, r = 1) and calls the solve's launcher:
+ *   ACE_NMS_INIT  Xinit [b][n], P0 = A X_init [b][m] -> Eo_out (zeros), AEo_out (= P0), state_out (na, naz, nbeta,
+ *                 nep2, nx0, nopt_a, ncur_a), flags_out (dpend)
+ *   ACE_NMS_STEP  the dense G = (I + K)^-1 and K = A A^H [m][m] are packed in matrix-core fragment order, then one
+ *                 iteration `it` (>= 1): Yo (Y of the previous iterate), M, B [b][m] doubles, Eo, AEo, state, flags;
+ *                 Yn (the iterate before Yo) is read only where a convergence test is pending (flags dpend)
+ *                 -> Yn_out (Y_new), M_out, En_out, AEn_out, optW_out, optY_out, curW_out, state_out, flags_out
+ *   ACE_NMS_FIN   only the convergence tests left pending: K, Yo, Yn, state, flags -> state_out, flags_out
+ *   ACE_NMS_OUT   Xinit, state (opt_obj, nopt_a, ncur_a), optW, curW -> V [b][n] (the X_init part of the selected
+ *                 iterate), Wsel [b][m] (its m-part; the caller adds A^H Wsel)
+ * All arrays are HOST; c128 as (re, im) doubles.  A per-realisation vector array the caller leaves NULL starts from
+ * `sentinel` on the device, En / AEn / V / Wsel always do, and every one of them is followed by `guard` doubles of
+ * `sentinel`: an output array has its rows and then the guard, so untouched memory can be asserted.  The arrays a
+ * kernel must not write (B, Yo, Eo, AEo) come back as well.  Outputs may be NULL.
+ *   state, state_out [batch][ACE_NMS_NSTATE]: mu, last_res, opt_obj, na, naz, nbeta, nep2, nopt_a, ncur_a, pd_dZ2,
+ *          pd_nZ2, pd_rc, obj2, nAX2, nY2, nJM2, dY2, dAtY, nAtY, nx0   (NULL state: zeros, mu = 1)
+ *   flags, flags_out [batch][ACE_NMS_NFLAG]: iters, done, status, dpend
+ *   done_count / done_count_out: the batch's count of stopped realisations before / after
+ *   guard_ok: 1 when the control block after the batch's and every control-block field not listed above are as
+ *          they were
+ * The state passes through exactly, so a caller chains init, steps, fin and out by handing the outputs back with
+ * the ping-pong pairs (Yo / Yn, Eo / En, AEo / AEn) swapped.
+ * Checked before any HIP call: ACE_ERR_ARG for an unknown op, batch, n or m < 1, a negative guard, rho <= 0
+ * (step, fin), it < 1 (step) and a NULL required array (named in ace_last_error()); ACE_ERR_UNSUPPORTED for
+ * m > 256 and for a refused LDS request.  Synchronous; allocates its own device memory. */
+enum { ACE_NMS_INIT = 0, ACE_NMS_STEP, ACE_NMS_FIN, ACE_NMS_OUT, ACE_NMS_NOPS };
+#define ACE_NMS_NSTATE 20
+#define ACE_NMS_NFLAG 4
+typedef struct ace_nms_args {
+    int32_t op, batch, n, m, it, fixed_iters, guard, done_count;
+    double tol_rel, tol_abs, rho, sentinel;
+    const double *Xinit, *P0, *G, *K, *B, *Yo, *Yn, *M, *Eo, *AEo, *optW, *optY, *curW, *state;
+    const int32_t* flags;
+    double *B_out, *Yo_out, *Yn_out, *M_out, *Eo_out, *En_out, *AEo_out, *AEn_out, *optW_out, *optY_out, *curW_out;
+    double *V, *Wsel, *state_out;
+    int32_t *flags_out, *done_count_out, *guard_ok;
+} ace_nms_args;
+int ace_nms_host(const ace_nms_args* args);
 
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(
