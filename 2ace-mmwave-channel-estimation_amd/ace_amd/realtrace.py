@@ -53,10 +53,12 @@ def split_rows(P, test_rows=None, n_test=None):
     return pool, test
 
 
-def train_rows(pool, M, k, rows="first", seed=0):
+def train_rows(pool, M, k, rows="first", seed=0, cb=None):
     """The M training rows of sweep point k: ``rows="first"`` the pool's first M (picked_beams = 1:M,
     Generate_Sensing_Matrix_with_candidate.m:12); ``rows="randperm"`` pool[engine.randperm(seed, k, len(pool), M)]
-    (the drivers' choice)."""
+    (the drivers' choice); ``rows="aopt"`` the Bayesian A-optimal choice among the pool's rows of the codebook ``cb``
+    [P][n] (the 'Bayes_Beam' mode, :14: ``design.bayes_beam(cb, M, seed=seed, stream_id=k, candidates=pool)``, on the
+    GPU; a row may come back more than once, as in the reference)."""
     pool = np.asarray(pool, dtype=np.int64)
     M = int(M)
     if not 1 <= M <= pool.size:
@@ -65,7 +67,13 @@ def train_rows(pool, M, k, rows="first", seed=0):
         return pool[:M].copy()
     if rows == "randperm":
         return pool[randperm(seed, k, pool.size, M).astype(np.int64)]
-    raise ValueError(f"rows must be 'first' or 'randperm', got {rows!r}")
+    if rows == "aopt":
+        if cb is None:
+            raise ValueError("rows='aopt' needs the codebook cb")
+        from .design import bayes_beam
+        dev = cb.device if hasattr(cb, "device") and not isinstance(cb, np.ndarray) else None
+        return bayes_beam(cb, M, seed=seed, stream_id=k, candidates=pool, device=dev)
+    raise ValueError(f"rows must be 'first', 'randperm' or 'aopt', got {rows!r}")
 
 
 def next_m(M, err, m_max=80, threshold=0.2):
@@ -134,7 +142,7 @@ def vs_m(cb, rss_dbm, tx, rx, M_list, *, test_rows=None, n_test=None, rows="firs
     status = np.empty((len(Ms), T), np.uint32)
     used, Xs = [], []
     for k, M in enumerate(Ms):
-        rk = train_rows(pool, M, k, rows, seed)
+        rk = train_rows(pool, M, k, rows, seed, cb=cb)
         used.append(rk)
         ridx = torch.as_tensor(rk, device=dev)
         A = cb[ridx].contiguous()

@@ -864,6 +864,48 @@ int ace_minl2_solve_host(const ace_minl2_cfg* cfg, int batch, int m, int n, cons
                          const int32_t* train_idx, double* X, double* Y, double* quality, int32_t* stage_iters,
                          int32_t* r_used, uint32_t* status);   /* host arrays; allocates, copies, synchronous */
 
+/* ---- batched Bayesian A-optimal probe selection (Bayes_Beam.m:12 -> bayesAopt_complex.m:105-254) -------------
+ * A Fedorov row exchange: pick nrows rows of the candidate codebook F [P][n] (c128, row-major, shared by the designs
+ * of a call) that minimise trace((X^H X + kdiag I)^-1), the posterior variance of the channel estimate, with A = I
+ * and no fixed rows as Bayes_Beam.m calls it.  Passes over the rows repeat while some row switched and
+ * iter < maxiter; a row switches to the candidate of the smallest exchange value a when a < acutoff or the row is
+ * still unassigned; ties go to the smaller candidate index (MATLAB's min), and duplicated candidate rows compare
+ * equal.  csrc/ace_aopt.hip states the step and the kernels (the candidate sweeps run on the f64 matrix cores).
+ * Design d has nrows[d] rows (1 .. nrows_max) and starts from the candidates init[d][0 .. nrows[d]) (an input, as
+ * train_idx is elsewhere: MATLAB's unidrnd stream cannot be reproduced; the entries may repeat).
+ * Outputs, DEVICE arrays: rowlist [designs][nrows_max] int32 (the candidate of every design row, -1 past nrows[d]),
+ * acrit [designs][2] f64 (trace of the start's inverse, tracked value at the end), iters and switches [designs] int32
+ * (passes run, rows switched), status [designs] uint32 (may be NULL), Minv_out NULL or [designs][n][n] c128 (the
+ * tracked inverse of the final design).
+ *   ACE_ST_AOPT_SINGULAR  1 - Re(x^H Minv x) of a row to remove was not positive and finite (or no exchange value
+ *                         was): the design stopped there with its rows as they stand; the other designs go on.
+ * A design's outputs are a function of (F, its nrows, its init, cfg) alone: not of the batch, of its place in it or
+ * of Minv_out.  workspace: ace_aopt_workspace_size(designs, P, n, nrows_max) bytes of DEVICE memory (the inverses
+ * and the start's scratch dominate: 16 n (n + min(nrows_max, n)) B per design); ACE_ERR_WORKSPACE when NULL or shorter.  The call enqueues on stream and
+ * synchronises it once per pass (the test whether any design goes on); no allocation.
+ * Limits: 1 <= n <= 1024, 1 <= P <= 65536, 1 <= nrows_max <= 4096 (ACE_ERR_UNSUPPORTED above, ACE_ERR_ARG below);
+ * designs < 1, maxiter < 1, a kdiag that is not positive and finite, a non-finite acutoff and a NULL cfg, F, nrows,
+ * init, rowlist, acrit, iters or switches return ACE_ERR_ARG; all of it before any HIP call.
+ * ace_aopt_workspace_size returns 0 for sizes outside the limits.  nrows and init of ace_aopt_select_batch are device
+ * arrays and cannot be checked there: the kernels clamp them into 1 .. nrows_max and 0 .. P - 1, so nothing is read
+ * out of bounds.  ace_aopt_select_host checks them (ACE_ERR_ARG). */
+#define ACE_ST_AOPT_SINGULAR 65536u
+typedef struct ace_aopt_cfg {
+    int maxiter;      /* passes over the rows, >= 1 (reference: 5) */
+    int reserved;
+    double kdiag;     /* kappa of K = kappa I (Bayes_Beam.m: 1) */
+    double acutoff;   /* a row switches when its exchange value is below this (reference: -sqrt(eps)) */
+} ace_aopt_cfg;
+void ace_aopt_cfg_default(ace_aopt_cfg* cfg);   /* 5, kappa = 1, -sqrt(eps) */
+size_t ace_aopt_workspace_size(int designs, int P, int n, int nrows_max);
+int ace_aopt_select_batch(const ace_aopt_cfg* cfg, int designs, int P, int n, int nrows_max, const double* F,
+                          const int32_t* nrows, const int32_t* init, int32_t* rowlist, double* acrit, int32_t* iters,
+                          int32_t* switches, uint32_t* status, double* Minv_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int ace_aopt_select_host(const ace_aopt_cfg* cfg, int designs, int P, int n, int nrows_max, const double* F,
+                         const int32_t* nrows, const int32_t* init, int32_t* rowlist, double* acrit, int32_t* iters,
+                         int32_t* switches, uint32_t* status, double* Minv_out);   /* host arrays; allocates, copies, synchronous */
+
 /* ---- nuclear-norm prox (A2nuclear ArgMinZ / Shrink) ---------------------------------------
  *   Z = U * Shrink(S, tau) * V'  with [U,S,V] = svd(E)     inferLowRank_Nuclear.m:411-439
  * for a batch of n x r matrices E_b (DEVICE, c128, [batch][r][n]: column j of E_b at
