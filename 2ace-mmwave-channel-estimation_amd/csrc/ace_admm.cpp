@@ -91,6 +91,9 @@ void linops_carve(Carver& cv, bool shared, int batch, int m, int n, LinOps* L) {
 //                       on stderr at the end of the solve
 //   ACE_ZCERT=0         the four-wave Z-step (r-column stages) always runs its eigensolver (no Ky Fan
 //                       certificate)
+//   ACE_SETUP_OVERLAP=0 the operator setup on the caller's stream before init with a host read per flag
+//                       (default: on a side stream beside init for the unit solve on a shared A, and
+//                       two host round trips in every shared-A setup)
 struct Knobs {
     int zcompact = 0, cold_sync = 0, msp_fail_it = -1, gyf_ctl = 1, msr_start = 56, msr_retry = 8, msr_waves = 8;
     int tkeig = 6;
@@ -100,12 +103,13 @@ struct Knobs {
     bool r1lz = true;   // rank-one profile: top eigenpair by Lanczos in the one-wave Z-step (ACE_R1_LANCZOS=0: Jacobi)
     double msp_room = 32.0;
 };
+static bool knob_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
 static Knobs read_knobs() {
     Knobs k;
-    const auto on = [](const char* name) {
-        const char* e = getenv(name);
-        return !(e && e[0] == '0');
-    };
+    const auto on = knob_on;
     const auto num = [](const char* name, double dflt) {
         const char* e = getenv(name);
         return e ? atof(e) : dflt;
@@ -184,6 +188,39 @@ static int i8_setup(LinOps& L, hipStream_t st) {
     L.gyk_ok = L.i8ok && L.Gf && lds_ok_budget(gyk_budget(), gyk_lds_bytes(m));
     return ACE_OK;
 }
+// The same work in three parts, for a setup whose host reads ride on those of ns_inverse (two round
+// trips for the whole setup): the expansions of A are launched before the first read, that of K
+// after it (c^2 goes to the device as two 32-bit fills, not through the staging buffer), and the
+// flag of K's expansion is read with the inverse's final residual.
+static bool i8_wanted(const LinOps& L) { return L.shared && L.allow_i8 && !i8_disabled(); }
+static int i8_expand_a(LinOps& L, hipStream_t st) {
+    const int m = L.m, n = L.n;
+    L.i8ok = false;
+    ACE_HIP(hipMemsetAsync(L.LA8, 0, i8_frag_bytes(m, n), st));
+    ACE_HIP(hipMemsetAsync(L.LAH8, 0, i8_frag_bytes(n, m), st));
+    ACE_HIP(hipMemsetAsync(L.i8flag, 0, sizeof(int), st));
+    launch_max_abs(2LL * m * n, L.A, L.c8, st);
+    launch_i8_expand(m, n, L.A, L.c8, L.LA8, L.LAH8, L.i8flag, st);
+    return ACE_OK;
+}
+static int i8_expand_k(LinOps& L, int flag, double c, hipStream_t st) {
+    const int m = L.m;
+    L.i8ok = flag == 0 && c > 0.0 && std::isfinite(c) && lds_ok_budget(i8ah_budget(0), i8ah_lds_bytes(m)) &&
+             lds_ok_budget(i8ah_budget(2), i8ah_lds_bytes(m));
+    if (!L.i8ok) return ACE_OK;
+    const double c2 = c * c;
+    uint32_t w[2];
+    memcpy(w, &c2, sizeof c2);
+    for (int k = 0; k < 2; ++k)
+        ACE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<uint32_t*>(L.c8 + 1) + k), (int)w[k], 1, st));
+    ACE_HIP(hipMemsetAsync(L.LK8, 0, i8k_frag_bytes(m), st));
+    launch_i8k_expand(m, L.K, L.c8, L.LK8, L.i8flag, st);
+    return ACE_OK;
+}
+static void i8_finish(LinOps& L, int flag) {
+    L.i8ok = flag == 0;
+    L.gyk_ok = L.i8ok && L.Gf && lds_ok_budget(gyk_budget(), gyk_lds_bytes(L.m));
+}
 
 // G = (I + K)^{-1} of the shared K by Newton-Schulz on the matrix cores:
 //   X0 = 2/(1 + b) I  with b >= lambda_max(I + K) (Gershgorin) and lambda_min(I + K) >= 1,
@@ -197,7 +234,8 @@ static int i8_setup(LinOps& L, hipStream_t st) {
 // The iteration stops one step after max|S_k| < 1e-10 (the next step's error is ~1e-20, i.e.
 // converged to rounding).  A single Gauss-Jordan work-group on one CU took 5.2 ms for m = 256;
 // this takes a few dozen small GEMMs.
-int ns_inverse(LinOps& L, hipStream_t st) {
+// with_i8: the phase-code check and the int8 images ride on the two host reads (i8_expand_a / _k).
+int ns_inverse(LinOps& L, hipStream_t st, bool with_i8 = false) {
     const int m = L.m;
     const long long mm = (long long)m * m;
     double* Ap = L.ns;            // I + K
@@ -212,7 +250,16 @@ int ns_inverse(LinOps& L, hipStream_t st) {
     // (one host read instead of a read after every iteration); one more step, as below, and a
     // final check (the polling loop takes over if rounding kept it above the bound).
     double b = 0.0;
-    ACE_HIP(read_back(&b, flag + 1, sizeof(double), st));
+    if (with_i8) {
+        int pflag = 1;
+        double c = 0.0;
+        ACE_TRY(i8_expand_a(L, st));
+        const ReadItem rd[3] = {{&b, flag + 1, sizeof(double)}, {&pflag, L.i8flag, sizeof(int)}, {&c, L.c8, sizeof(double)}};
+        ACE_HIP(read_back_many(rd, 3, st));
+        ACE_TRY(i8_expand_k(L, pflag, c, st));
+    } else {
+        ACE_HIP(read_back(&b, flag + 1, sizeof(double), st));
+    }
     int kpred = 60;
     if (std::isfinite(b) && b >= 1.0) {
         const double rho = (b - 1.0) / (b + 1.0);
@@ -233,7 +280,14 @@ int ns_inverse(LinOps& L, hipStream_t st) {
     {   // check R of the last step (it is the residual of the iterate before it: converged one step earlier)
         double h = 0.0;
         launch_max_abs(2 * mm, R, flag, st);
-        ACE_HIP(read_back(&h, flag, sizeof(double), st));
+        if (with_i8 && L.i8ok) {
+            int kflag = 1;
+            const ReadItem rd[2] = {{&h, flag, sizeof(double)}, {&kflag, L.i8flag, sizeof(int)}};
+            ACE_HIP(read_back_many(rd, 2, st));
+            i8_finish(L, kflag);
+        } else {
+            ACE_HIP(read_back(&h, flag, sizeof(double), st));
+        }
         done = h < 1e-10;
     }
     for (; it < 60 && !done;) {   // (rounding kept the residual above the bound: poll as before)
@@ -281,6 +335,7 @@ int linops_setup(LinOps& L, int batch, hipStream_t st) {
     const int mats = L.shared ? 1 : batch;
     const long long mm = (long long)m * m, mn = (long long)m * n;
     ProfScope ps(ACE_K_SETUP, st);
+    const bool co = knob_on("ACE_SETUP_OVERLAP") && i8_wanted(L);   // the int8 setup inside ns_inverse's host reads
     if (!L.shared) {
         ACE_TRY(pc_setup(L, batch, st));
         if (L.pc_ok) return ACE_OK;
@@ -288,7 +343,7 @@ int linops_setup(LinOps& L, int batch, hipStream_t st) {
     // K[j][i] = sum_k conj(A[i][k]) A[j][k]  : GEMM with L = conj(A), V = rows of A
     launch_zgemm(0, true, m, n, m, L.A, n, mn, L.A, n, mn, L.K, nullptr, m, mm, mats, st);
     if (L.shared) {
-        ACE_TRY(ns_inverse(L, st));
+        ACE_TRY(ns_inverse(L, st, co));
     } else {  // one Gauss-Jordan work-group per realisation's matrix (parallel over the batch)
         ACE_HIP(hipMemcpyAsync(L.G, L.K, sizeof(double) * 2 * mm * mats, hipMemcpyDeviceToDevice, st));
         launch_inv_ipk(m, mats, L.G, mm, st);
@@ -300,7 +355,7 @@ int linops_setup(LinOps& L, int batch, hipStream_t st) {
             launch_gyk_gfrag(m, L.G, L.Gf, st);
             launch_gyk_gfrag(m, L.K, L.Kfr, st);
         }
-        ACE_TRY(i8_setup(L, st));
+        if (!co) ACE_TRY(i8_setup(L, st));
     }
     ACE_LAUNCHED("operator setup (K, G, A^H, fragments, digit planes)");
     return ACE_OK;
@@ -378,23 +433,21 @@ static AdmmState state_slice(const AdmmState& w, long long ob, int m, int n, int
     return h;
 }
 
-static int admm_iterate_split(const LinOps& L, const AdmmParams& p, const AdmmState& w, const ZArgs& za0, int batch,
-                              const double* B, int nsplit, const Knobs& kn, double* Xo, double* Yo, int32_t* iters,
-                              uint32_t* status, double* mu_out, hipStream_t st) {
-    const int m = L.m, n = L.n;
-    const int chunk = (batch / nsplit + 15) & ~15;
-    // The sub-batch streams and fork / join events outlive the solve (one set per device and caller
-    // stream): destroying a stream waits for its work, which would make every solve block the host
-    // until the GPU finishes it (measured: a 0.7 ms idle gap before the next solve's first kernel).
-    // Keyed by (device, caller stream), so solves on different caller streams stay independent; at
-    // most kSplitSets sets are kept, the least recently used one is released when a new caller
-    // stream needs a set (a caller that makes a stream per solve recycles them).  A set only holds
-    // library-owned streams, so a caller stream handle that is destroyed and reused stays correct.
-    struct SplitRes {
-        hipStream_t s[4] = {};
-        hipEvent_t e[4] = {}, c[4] = {};
-        unsigned long long used = 0;
-    };
+// The sub-batch streams and fork / join events outlive the solve (one set per device and caller
+// stream): destroying a stream waits for its work, which would make every solve block the host
+// until the GPU finishes it (measured: a 0.7 ms idle gap before the next solve's first kernel).
+// Keyed by (device, caller stream), so solves on different caller streams stay independent; at
+// most kSplitSets sets are kept, the least recently used one is released when a new caller
+// stream needs a set (a caller that makes a stream per solve recycles them).  A set only holds
+// library-owned streams, so a caller stream handle that is destroyed and reused stays correct.
+// The set also serves the operator setup beside init (stream 1 is idle before the fork; f: its fork
+// and join events).
+struct SplitRes {
+    hipStream_t s[4] = {};
+    hipEvent_t e[4] = {}, c[4] = {}, f[2] = {};
+    unsigned long long used = 0;
+};
+static int split_acquire(hipStream_t st, SplitRes* out) {
     constexpr size_t kSplitSets = 8;
     static std::map<std::pair<int, hipStream_t>, SplitRes> res;
     static unsigned long long tick = 0;
@@ -405,44 +458,55 @@ static int admm_iterate_split(const LinOps& L, const AdmmParams& p, const AdmmSt
             if (r.e[h]) (void)hipEventDestroy(r.e[h]);
             if (r.c[h]) (void)hipEventDestroy(r.c[h]);
         }
+        for (int h = 0; h < 2; ++h)
+            if (r.f[h]) (void)hipEventDestroy(r.f[h]);
         r = SplitRes{};
     };
     int dev = 0;
     ACE_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mtx);
+    const auto key = std::make_pair(dev, st);
+    auto it = res.find(key);
+    if (it == res.end()) {
+        if (res.size() >= kSplitSets) {
+            auto lru = res.begin();
+            for (auto i = res.begin(); i != res.end(); ++i)
+                if (i->second.used < lru->second.used) lru = i;
+            release(lru->second);
+            res.erase(lru);
+        }
+        SplitRes r;
+        hipError_t e = hipSuccess;
+        for (int h = 0; h < 4 && e == hipSuccess; ++h) {
+            e = hipEventCreateWithFlags(&r.e[h], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&r.c[h], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipStreamCreateWithFlags(&r.s[h], hipStreamNonBlocking);
+        }
+        for (int h = 0; h < 2 && e == hipSuccess; ++h) e = hipEventCreateWithFlags(&r.f[h], hipEventDisableTiming);
+        if (e != hipSuccess) {
+            release(r);
+            return fail(ACE_ERR_HIP, "sub-batch streams: %s", hipGetErrorString(e));
+        }
+        it = res.emplace(key, r).first;
+    }
+    it->second.used = ++tick;
+    *out = it->second;
+    return ACE_OK;
+}
+
+static int admm_iterate_split(const LinOps& L, const AdmmParams& p, const AdmmState& w, const ZArgs& za0, int batch,
+                              const double* B, int nsplit, const Knobs& kn, double* Xo, double* Yo, int32_t* iters,
+                              uint32_t* status, double* mu_out, hipStream_t st) {
+    const int m = L.m, n = L.n;
+    const int chunk = (batch / nsplit + 15) & ~15;
+    SplitRes sr;
+    ACE_TRY(split_acquire(st, &sr));
     std::vector<hipStream_t> ss(nsplit, st);
     std::vector<hipEvent_t> ev(nsplit), cev(nsplit);
-    {
-        std::lock_guard<std::mutex> lk(mtx);
-        const auto key = std::make_pair(dev, st);
-        auto it = res.find(key);
-        if (it == res.end()) {
-            if (res.size() >= kSplitSets) {
-                auto lru = res.begin();
-                for (auto i = res.begin(); i != res.end(); ++i)
-                    if (i->second.used < lru->second.used) lru = i;
-                release(lru->second);
-                res.erase(lru);
-            }
-            SplitRes r;
-            hipError_t e = hipSuccess;
-            for (int h = 0; h < 4 && e == hipSuccess; ++h) {
-                e = hipEventCreateWithFlags(&r.e[h], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&r.c[h], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipStreamCreateWithFlags(&r.s[h], hipStreamNonBlocking);
-            }
-            if (e != hipSuccess) {
-                release(r);
-                return fail(ACE_ERR_HIP, "sub-batch streams: %s", hipGetErrorString(e));
-            }
-            it = res.emplace(key, r).first;
-        }
-        SplitRes& r = it->second;
-        r.used = ++tick;
-        for (int h = 0; h < nsplit; ++h) {
-            ev[h] = r.e[h];
-            cev[h] = r.c[h];
-            if (h > 0) ss[h] = r.s[h];
-        }
+    for (int h = 0; h < nsplit; ++h) {
+        ev[h] = sr.e[h];
+        cev[h] = sr.c[h];
+        if (h > 0) ss[h] = sr.s[h];
     }
     ACE_HIP(hipEventRecord(ev[0], st));   // fork after init
     for (int h = 1; h < nsplit; ++h) ACE_HIP(hipStreamWaitEvent(ss[h], ev[0], 0));
@@ -749,9 +813,13 @@ static int tk_report(const Knobs& kn, const AdmmState& w, int rc, hipStream_t st
     return rc;
 }
 
-int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& w, int batch, const double* B,
-             const double* X0, double* Xo, double* Yo, int32_t* iters, uint32_t* status, double* mu_out,
-             hipStream_t st) {
+// setup: the operators of *setup are still to be built (admm_setup_run's overlapped form): init is launched on
+// st first, linops_setup runs on the side stream meanwhile, and st waits for it before the first launch that
+// reads one of its products.  Only for a shared A at r = 1, A2only, where init reads none of them and takes no
+// decision from the setup's flags.
+static int admm_run_impl(const LinOps& L, LinOps* setup, const AdmmParams& p, const AdmmState& w, int batch,
+                         const double* B, const double* X0, double* Xo, double* Yo, int32_t* iters,
+                         uint32_t* status, double* mu_out, hipStream_t st) {
     const int m = L.m, n = L.n, r = p.r;
     const Knobs kn = read_knobs();
     if (!L.shared && r != 1) return fail(ACE_ERR_UNSUPPORTED, "private sensing matrices support r = 1 only");
@@ -762,18 +830,24 @@ int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& w, int batch
     const long long mm = (long long)m * m, mn = (long long)m * n;
     const bool fast = (r == 1);                       // r = 1 kernels (ystep, one-wave zstep)
     const bool fused = fast && L.shared;              // pre_kernel folded into the shared-A GEMMs
-    // phase-code A: int8 digit-plane applies; apply_AH writes W = A^H g and the Z-step forms X
-    const bool i8 = fused && L.i8ok && zstep_takes_w(p.variant, r);
-    const bool gyk = i8 && L.gyk_ok;                  // g, Y-step, K Y and the dual terms in one kernel
-    // private phase-code codebooks: T, g = G T, Y-step, W = A^H g and the dual terms in one kernel
-    const bool pc = !L.shared && L.pc_ok && r == 1 && zstep_takes_w(p.variant, r);
-    const bool wmode = i8 || pc;
-    // r-column stages on a shared phase-code A: A V, A^H g and K Y as exact int8 digit planes over
-    // the batch * r vectors (vector j of realisation j / r), G T and the rest unchanged
-    const bool i8r = !fast && L.shared && L.i8ok && kn.i8r && nv >= 256;
-    g_path[(i8 || i8r) ? 0 : pc ? 1 : L.shared ? 2 : 3].fetch_add(1, std::memory_order_relaxed);
-    // pc_ok means K and G hold the code-image path's tiles, not the m x m matrices the generic path reads
-    if (L.pc_ok && !pc) return fail(ACE_ERR_UNSUPPORTED, "private phase-code setup without its iteration path");
+    // The paths the setup's flags select (with `setup`, known only once it has run: until then all false)
+    bool i8 = false, gyk = false, pc = false, wmode = false, i8r = false;
+    auto paths = [&]() -> int {
+        // phase-code A: int8 digit-plane applies; apply_AH writes W = A^H g and the Z-step forms X
+        i8 = fused && L.i8ok && zstep_takes_w(p.variant, r);
+        gyk = i8 && L.gyk_ok;                  // g, Y-step, K Y and the dual terms in one kernel
+        // private phase-code codebooks: T, g = G T, Y-step, W = A^H g and the dual terms in one kernel
+        pc = !L.shared && L.pc_ok && r == 1 && zstep_takes_w(p.variant, r);
+        wmode = i8 || pc;
+        // r-column stages on a shared phase-code A: A V, A^H g and K Y as exact int8 digit planes over
+        // the batch * r vectors (vector j of realisation j / r), G T and the rest unchanged
+        i8r = !fast && L.shared && L.i8ok && kn.i8r && nv >= 256;
+        g_path[(i8 || i8r) ? 0 : pc ? 1 : L.shared ? 2 : 3].fetch_add(1, std::memory_order_relaxed);
+        // pc_ok means K and G hold the code-image path's tiles, not the m x m matrices the generic path reads
+        if (L.pc_ok && !pc) return fail(ACE_ERR_UNSUPPORTED, "private phase-code setup without its iteration path");
+        return ACE_OK;
+    };
+    if (!setup) ACE_TRY(paths());
 
     auto applyA = [&](int mode, const double* Vin, double* C, const double* E) {  // C = E (-) A Vin
         if (L.shared) launch_zgemm(mode, false, m, n, nv, L.A, n, 0, Vin, n, 0, C, E, m, 0, 1, st);
@@ -830,20 +904,51 @@ int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& w, int batch
     // A2nuclear r = 1 on a shared A: the m-space iteration (ace_nucmsp.hip)
     const bool nms = L.shared && L.frag_ok && r == 1 && p.variant == ACE_VARIANT_NUCLEAR && kn.nuc_msp && nms_supported(m);
     // ---- init (:296-310)
-    ACE_HIP(hipMemsetAsync(w.done, 0, 256, st));
-    ACE_HIP(hipMemsetAsync(w.zeros, 0, 16 * (size_t)n, st));
-    {
-        ProfScope ps(ACE_K_INIT, st);
-        if (pc) launch_pc_apply_a(batch, m, n, L.pcodes + pc_codesA_off(batch, m, n), L.pcb, X0, w.T, st);
-        else applyA(0, X0, w.T, nullptr);                        // AX = A*X0
-        launch_init_r(row_mode, n, m, r, batch, X0, w.T, B, w.X, w.Y[0], w.M, w.N, w.st, p.mu0, st, p.part);
-        if (!nms) {
-            za.it = 0;
-            launch_zstep(p.variant, true, za, batch, st);           // Z = ArgMinZ(X, N=0, mu=1)
-            if (!pc && !za.lazy_dual) applyMM(L.K, w.Y[0], w.KY[0]); // K*Y (for A'*Y terms; lazy: on demand)
+    auto init = [&]() -> int {
+        ACE_HIP(hipMemsetAsync(w.done, 0, 256, st));
+        ACE_HIP(hipMemsetAsync(w.zeros, 0, 16 * (size_t)n, st));
+        {
+            ProfScope ps(ACE_K_INIT, st);
+            if (pc) launch_pc_apply_a(batch, m, n, L.pcodes + pc_codesA_off(batch, m, n), L.pcb, X0, w.T, st);
+            else applyA(0, X0, w.T, nullptr);                        // AX = A*X0
+            launch_init_r(row_mode, n, m, r, batch, X0, w.T, B, w.X, w.Y[0], w.M, w.N, w.st, p.mu0, st, p.part);
+            if (!nms) {
+                za.it = 0;
+                launch_zstep(p.variant, true, za, batch, st);           // Z = ArgMinZ(X, N=0, mu=1)
+                // K*Y (for A'*Y terms; lazy: on demand); with `setup`, once K is there
+                if (!setup && !pc && !za.lazy_dual) applyMM(L.K, w.Y[0], w.KY[0]);
+            }
+        }
+        ACE_LAUNCHED("init (A X0, init, Z-step)");
+        return ACE_OK;
+    };
+    if (!setup) {
+        ACE_TRY(init());
+    } else {
+        // The side stream starts behind the caller's earlier work (a previous solve may still read the
+        // operators this setup rewrites, and A itself comes from that stream); every return from here on
+        // passes the join below.
+        SplitRes sr;
+        ACE_TRY(split_acquire(st, &sr));
+        ACE_HIP(hipEventRecord(sr.f[0], st));
+        ACE_HIP(hipStreamWaitEvent(sr.s[1], sr.f[0], 0));
+        int rc = init();
+        if (rc == ACE_OK) rc = linops_setup(*setup, batch, sr.s[1]);
+        const hipError_t je = hipEventRecord(sr.f[1], sr.s[1]);
+        const hipError_t jw = je == hipSuccess ? hipStreamWaitEvent(st, sr.f[1], 0) : je;
+        if (rc) return rc;
+        if (jw != hipSuccess) {
+            (void)hipStreamSynchronize(sr.s[1]);
+            return fail(ACE_ERR_HIP, "setup join: %s", hipGetErrorString(jw));
+        }
+        ACE_TRY(paths());
+        za.lazy_dual = (gyk && kn.lazy_dual) ? 1 : 0;
+        if (!za.lazy_dual) {
+            ProfScope ps(ACE_K_INIT, st);
+            applyMM(L.K, w.Y[0], w.KY[0]);
+            ACE_LAUNCHED("init (K Y)");
         }
     }
-    ACE_LAUNCHED("init (A X0, init, Z-step)");
     if (nms) return admm_nuclear_msp(L, p, w, za, batch, B, Xo, Yo, iters, status, mu_out, st);
 
     int q = 0;
@@ -1009,6 +1114,31 @@ int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& w, int batch
     }
     ACE_LAUNCHED("finalize");
     return tk_report(kn, w, ACE_OK, st);
+}
+
+int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& w, int batch, const double* B,
+             const double* X0, double* Xo, double* Yo, int32_t* iters, uint32_t* status, double* mu_out,
+             hipStream_t st) {
+    return admm_run_impl(L, nullptr, p, w, batch, B, X0, Xo, Yo, iters, status, mu_out, st);
+}
+
+int admm_setup_run(LinOps& L, const AdmmParams& p, const AdmmState& w, int batch, const double* B,
+                   const double* X0, double* Xo, double* Yo, int32_t* iters, uint32_t* status, double* mu_out,
+                   hipStream_t st, bool may_overlap) {
+    bool overlap = may_overlap && knob_on("ACE_SETUP_OVERLAP") && L.shared && p.r == 1 &&
+                   p.variant == ACE_VARIANT_A2ONLY && !p.part;
+    if (overlap) {   // a capturing stream keeps the serial order (whose host reads refuse the capture)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+            (void)hipGetLastError();
+            overlap = false;
+        } else if (cs != hipStreamCaptureStatusNone) {
+            overlap = false;
+        }
+    }
+    if (overlap) return admm_run_impl(L, &L, p, w, batch, B, X0, Xo, Yo, iters, status, mu_out, st);
+    ACE_TRY(linops_setup(L, batch, st));
+    return admm_run_impl(L, nullptr, p, w, batch, B, X0, Xo, Yo, iters, status, mu_out, st);
 }
 
 }  // namespace ace

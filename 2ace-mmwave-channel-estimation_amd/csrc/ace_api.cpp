@@ -311,7 +311,6 @@ int solve_core(const ace_admm_cfg* cfg, int batch, int m, int n, int tx, int rx,
     admm_state_carve(cv, batch, m, n, cols(cfg), &w);
     L.A = A;
     L.allow_i8 = cfg->f64_applies == 0;
-    ACE_TRY(linops_setup(L, batch, st));
     AdmmParams p{};
     p.variant = cfg->variant;
     p.r = cols(cfg);
@@ -329,7 +328,8 @@ int solve_core(const ace_admm_cfg* cfg, int batch, int m, int n, int tx, int rx,
     p.prof_n = prof_n;
     p.use_rank_one = cfg->use_rank_one;
     p.rank_one = cfg->rank_one;
-    return admm_run(L, p, w, batch, B, X0, Xo, Yo, iters, status, mu_out, st);
+    // (the odd-tx entry's padded solve keeps the serial order: prof_tx is set there only)
+    return admm_setup_run(L, p, w, batch, B, X0, Xo, Yo, iters, status, mu_out, st, prof_tx == 0);
 }
 }  // namespace
 

@@ -98,6 +98,29 @@ inline hipError_t read_back(void* dst, const void* src, size_t bytes, hipStream_
     if (e == hipSuccess) memcpy(dst, g_stage.p, bytes);
     return e;
 }
+// Several small device arrays in one host round trip (consecutive 16-byte slots of the staging buffer).
+struct ReadItem {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+inline hipError_t read_back_many(const ReadItem* rd, int cnt, hipStream_t st) {
+    size_t tot = 0;
+    for (int i = 0; i < cnt; ++i) tot += (rd[i].bytes + 15) & ~(size_t)15;
+    hipError_t e = g_stage.reserve(tot);
+    size_t off = 0;
+    for (int i = 0; i < cnt && e == hipSuccess; ++i) {
+        e = hipMemcpyAsync(static_cast<char*>(g_stage.p) + off, rd[i].src, rd[i].bytes, hipMemcpyDeviceToHost, st);
+        off += (rd[i].bytes + 15) & ~(size_t)15;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    off = 0;
+    for (int i = 0; i < cnt && e == hipSuccess; ++i) {
+        memcpy(rd[i].dst, static_cast<char*>(g_stage.p) + off, rd[i].bytes);
+        off += (rd[i].bytes + 15) & ~(size_t)15;
+    }
+    return e;
+}
 inline hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t st) {
     hipError_t e = g_stage.reserve(bytes);
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the staging buffer may still be in use)
@@ -317,5 +340,11 @@ void admm_state_carve(Carver& cv, int batch, int m, int n, int r, AdmmState* s);
 int admm_run(const LinOps& L, const AdmmParams& p, const AdmmState& s, int batch, const double* B,
              const double* X0, double* Xo, double* Yo, int32_t* iters, uint32_t* status, double* mu,
              hipStream_t st);
+// linops_setup(L), then admm_run.  may_overlap: a unit solve on a shared A (r = 1, A2only) builds the operators
+// on a library-owned side stream while init runs on st (ACE_SETUP_OVERLAP=0: never); the call stays
+// stream-ordered on st for the caller.
+int admm_setup_run(LinOps& L, const AdmmParams& p, const AdmmState& s, int batch, const double* B,
+                   const double* X0, double* Xo, double* Yo, int32_t* iters, uint32_t* status, double* mu,
+                   hipStream_t st, bool may_overlap);
 
 }  // namespace ace
