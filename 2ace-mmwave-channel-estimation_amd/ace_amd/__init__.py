@@ -32,5 +32,8 @@ from . import stages, nms  # noqa: F401
 from .design import aopt_select_batch, aopt_select_host, bayes_beam, AoptResult  # noqa: F401
 from ._lib import ACE_ST_AOPT_SINGULAR, AoptCfg, aopt_cfg  # noqa: F401
 from . import design  # noqa: F401
+from .scenario import scenario_batch, ScenarioResult  # noqa: F401
+from ._lib import ScenarioCfg, scenario_cfg  # noqa: F401
+from . import scenario  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

@@ -11,6 +11,7 @@ peaks where both steering vectors match.
 Noise model.  The reference's sweep measures ``FW vec(H) + W' * noiseMatrix`` (Generate_Measurement.m); the
 build's synth draws iid measurement noise CN(0, 10^(-SNR/10)) per probe, and ``beam_sweep`` keeps to the synth's
 model: one iid draw per beam pair.
+The reference's own model is noise model 1 of ``scenario.scenario_batch`` (``ace_synth_scenario``), on ``kron_codebook``.
 """
 from __future__ import annotations
 
@@ -73,6 +74,18 @@ def sweep_beams(n_ant, M, search_deg=SEARCH_DEG):
     part = np.linspace(-0.5 * search_deg, 0.5 * search_deg, int(M) + 1)
     centres = 0.5 * (part[:-1] + part[1:])
     return quantize_ps(steering(n_ant, np.sin(np.deg2rad(centres))) * np.sqrt(n_ant)), centres
+
+
+def kron_codebook(Ft, Wr):
+    """The measurement matrix kron(F.', W') of Generate_Sensing_Matrix.m for precoders Ft [Mt][tx] and combiners Wr
+    [Mr][rx] given as rows: A [Mt*Mr][tx*rx] with A[it Mr + q][t rx + r] = Ft[it][t] conj(Wr[q][r]), the synth's vec(H)
+    order (element r + rx t), so (A vecH)[it Mr + q] = w_q^H H f_it.  ``sweep_beams`` is Directional_Beam_Angular.m's
+    beam set (the steering vectors at the centres of M equal partitions of the searching area, quantised to 2 bits);
+    the reference's 'Directional_Beam_Angular' codebook is ``kron_codebook(sweep_beams(tx, Mt, deg)[0] / sqrt(tx),
+    sweep_beams(rx, Mr, deg)[0] / sqrt(rx))``."""
+    Ft, Wr = np.atleast_2d(np.asarray(Ft, np.complex128)), np.atleast_2d(np.asarray(Wr, np.complex128))
+    A = Ft[:, None, :, None] * np.conj(Wr)[None, :, None, :]           # [it][q][t][r]
+    return np.ascontiguousarray(A.reshape(Ft.shape[0] * Wr.shape[0], Ft.shape[1] * Wr.shape[1]))
 
 
 def _scan(X, W0, F1, noise=None, **kw):

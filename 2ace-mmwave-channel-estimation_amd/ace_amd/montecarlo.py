@@ -14,6 +14,9 @@ therefore always solves whole chunks of ``chunk`` consecutive realisations on th
 realisation index (realisation i belongs to chunk i // chunk, whatever ``first`` and ``count``), and keeps
 the rows asked for: a realisation's metrics are a function of (seed, M, i, chunk) alone, and any shard
 reproduces its rows of the full run bit for bit.
+
+``vs_snr`` is the sweep over SNR of ``Vs_SNR.m`` in the reference's own scenario (``scenario.scenario_batch``), on the
+same chunk grid.
 """
 from __future__ import annotations
 
@@ -346,3 +349,122 @@ def vs_m_baselines(tx, rx, M_list, count, *, method="A2only", snr_db=30.0, L=3, 
     return {"M": np.asarray(Ms, np.int64), "metrics": metrics, "status": status,
             "mean": metrics.mean(axis=1), "n_degenerate": ((status & ACE_ST_EVAL_DEGENERATE) != 0).sum(axis=1),
             "columns": METRICS, **base, "baseline_mean": {name: v.mean(axis=1) for name, v in base.items()}}
+
+
+VS_SNR_ADMM = ("A2only", "A2nuclear")
+VS_SNR_SPARSE = ("plomp", "plgamp", "perfect_cs", "noisy_cs")
+
+
+def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", "perfect_cs", "noisy_cs"), L=1,
+           rician_k=5, search_deg=40.0, on_grid=False, noise="combiner", seed, first=0, chunk=CHUNK, pl_maxits=4000,
+           maxiter=None, device=None) -> dict:
+    """The reference's ``Vs_SNR`` loop (Numerical_Simulation/main_programs/Vs_SNR.m:100-108: one dominant path with
+    ``rician_k`` NLOS paths at the 7 dB K-factor, a searching area of ``search_deg`` degrees, M x M directional beams)
+    with every step on the GPU: per SNR and realisation the scenario generator (``scenario.scenario_batch``), the
+    recoveries and ``evaluate_batch``.  Only metrics and status words leave the device.
+
+    What each method sees:
+
+      * the sparse methods (``plomp``, ``plgamp``, ``perfect_cs``, ``noisy_cs``: Method.PLOMP, PLGAMP, PerfectPhaseCS,
+        NoisyPhaseCS) the Kronecker codebook ``angular.kron_codebook`` of M x M ``angular.sweep_beams`` over
+        ``search_deg`` (Directional_Beam_Angular.m), Phi = A AD with ``sparse.dictionary_2d(..., search_deg=search_deg)``
+        and the measurements at the reference's own scale with noise model ``noise``: "combiner" is the reference's
+        W' * noiseMatrix, "iid" one draw per probe.  M^2 may not exceed the OMP kernel's row limit;
+      * the ADMM methods (``A2only``, ``A2nuclear``) a random phase-code codebook of M^2 rows with iid noise and the
+        normalised B (MyCPR.m hands them measurementMat_RB, and random beams have no combiner structure), through
+        ``vs_m``'s pipeline and train partitions.
+
+    Random numbers.  Realisation b of the call is realisation ``first + b`` of the sweep; its channel and its
+    unit-variance draws (noise, phase noise, start) depend on (seed, first + b) alone, so every SNR point sees the same
+    channel and the same noise direction scaled by its sigma.  This is common random numbers; it departs from the
+    reference, which draws afresh at every point.  Chunks lie on ``vs_m``'s grid (realisation i belongs to chunk
+    i // chunk), so a shard reproduces its rows of the full run bit for bit.
+
+    Returns ``snr`` [nSNR], per method its four ``evaluate_batch`` columns [nSNR][count][4] (key = the method's name),
+    ``status_<method>`` [nSNR][count], ``mean`` (per method [nSNR][4]), ``gain_percsi_ana`` [nSNR][count]
+    (``evaluate_batch(H, H)`` on the channel at the reference's scale), ``mCS`` and ``columns``."""
+    import torch
+    from . import angular, sparse
+    from .engine import randperm
+    from .pipeline import infer_low_rank_pipeline_batch
+    from .scenario import scenario_batch
+    from ._lib import LIB, check, scenario_cfg
+    from .solver import VARIANTS
+    methods = tuple(methods)
+    bad = [k for k in methods if k not in VS_SNR_ADMM + VS_SNR_SPARSE]
+    if bad or not methods:
+        raise ValueError(f"methods must come from {VS_SNR_ADMM + VS_SNR_SPARSE}, got {bad or methods}")
+    if tx != rx:
+        raise ValueError(f"vs_snr needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    if noise not in ("combiner", "iid"):
+        raise ValueError(f"noise must be 'combiner' or 'iid', got {noise!r}")
+    count, first, chunk, M = int(count), int(first), int(chunk), int(M)
+    if count < 1 or first < 0 or chunk < 1 or M < 1:
+        raise ValueError("count, chunk and M must be >= 1 and first >= 0")
+    m = M * M
+    sp = [k for k in methods if k in VS_SNR_SPARSE]
+    ad = [k for k in methods if k in VS_SNR_ADMM]
+    if sp and m > sparse.D_MAX:
+        raise ValueError(f"vs_snr: M = {M} gives M^2 = {m} measurements > {sparse.D_MAX}, the OMP kernel's row limit "
+                         f"(methods {sp})")
+    snrs = [float(v) for v in snr_list]
+    dev = torch.device("cuda" if device is None else device)
+    n, s = tx * rx, int(L)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    base = dict(L=int(L), rician_k=int(rician_k), search_deg=float(search_deg), on_grid=int(bool(on_grid)))
+    out = {k: np.empty((len(snrs), count, 4), np.float64) for k in methods}
+    stat = {k: np.zeros((len(snrs), count), np.uint32) for k in methods}
+    percsi = np.empty((len(snrs), count), np.float64)
+    mcs = 0
+    if sp:
+        Ft, Wr = angular.sweep_beams(tx, M, search_deg)[0] / np.sqrt(tx), angular.sweep_beams(rx, M, search_deg)[0] / np.sqrt(rx)
+        As, Wd = up(angular.kron_codebook(Ft, Wr)), up(Wr)
+        AD = up(sparse.dictionary_2d(tx, rx, search_deg=search_deg)[0])
+        Phi = (As @ AD).contiguous()
+        setup = sparse.two_stage_setup(Phi.cpu().numpy(), s).to(dev)
+        mcs = setup.mCS
+    if ad:
+        Ar = torch.empty((1, m, n), dtype=torch.complex128, device=dev)
+        check(LIB.ace_synth_codebook(seed, -1, 1, m, n, Ar.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        kw = {} if maxiter is None else {"maxiter": int(maxiter)}
+    end = first + count
+    for k, snr in enumerate(snrs):
+        for c0 in range(first // chunk * chunk, end, chunk):
+            lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+            rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
+            res = {}
+            if sp:
+                cfg = scenario_cfg(snr_db=snr, noise_model=1 if noise == "combiner" else 0, **base)
+                sc = scenario_batch(seed, c0, chunk, tx, rx, As, cfg, Wd if noise == "combiner" else None,
+                                    want=("vecH", "y", "y_noisy", "B_raw"))
+                H = sc.vecH
+                if "plomp" in sp or "plgamp" in sp:
+                    ts, sig = sparse.plomp_stage1(Phi, sc.B_raw * sc.B_raw, s, setup=setup, maxIts=int(pl_maxits))
+                    if "plomp" in sp:
+                        res["plomp"] = (sparse.omp_batch(ts.C, sig, ts.mCS, 1e-12), H)
+                    if "plgamp" in sp:
+                        res["plgamp"] = (sparse._gamp_stage2(ts, sig, s, sc.noise_power, Phi.shape[1]), H)
+                if "perfect_cs" in sp:
+                    res["perfect_cs"] = (sparse.perfect_phase_cs(Phi, sc.y, s), H)
+                if "noisy_cs" in sp:
+                    res["noisy_cs"] = (sparse.noisy_phase_cs(Phi, sc.y_noisy, s), H)
+            if ad:
+                sa = scenario_batch(seed, c0, chunk, tx, rx, Ar, scenario_cfg(snr_db=snr, noise_model=0, **base),
+                                    want=("vecH", "B", "Hn"))
+                H = sa.vecH
+                for name in ad:
+                    pc = pipeline_cfg(VARIANTS[name])
+                    R, mt = pc.restarts, math.floor(m * pc.cc_frac)
+                    tr = np.stack([np.stack([randperm(seed, (c0 + b) * R + i, m, mt) for i in range(R)])
+                                   for b in range(chunk)])
+                    res[name] = (infer_low_rank_pipeline_batch(Ar, sa.B, tx, rx, tr, variant=name, restarts=R, **kw), sa.Hn)
+            percsi[k, rows] = evaluate_batch(H, H, tx, rx).gain_ana[sel].cpu().numpy()
+            for name, (r, G) in res.items():
+                X = r.X if name in ad else r.channel(AD)
+                ev = evaluate_batch(X, G, tx, rx)
+                st = ev.status if name in ad else (ev.status | r.status)
+                out[name][k, rows] = ev.metrics[sel].cpu().numpy()
+                stat[name][k, rows] = st[sel].cpu().numpy().view(np.uint32)
+    return {"snr": np.asarray(snrs, np.float64), "M": M, "mCS": mcs, "s": s, **out, "columns": METRICS,
+            "gain_percsi_ana": percsi, **{f"status_{k}": v for k, v in stat.items()},
+            "mean": {k: v.mean(axis=1) for k, v in out.items()}}

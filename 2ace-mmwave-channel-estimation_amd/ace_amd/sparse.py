@@ -13,6 +13,8 @@ ADMM recoveries.
   * ``perfect_phase_cs``   -- ``Method.PerfectPhaseCS`` (My_Conventional_CS.m) on coherent (complex) measurements:
                               ``solver="omp"`` is its ``OMP(A, y, s)`` branch (:81), ``solver="embgamp"`` its first
                               branch, EMBGAMP with learn_lambda (:71-79).
+  * ``noisy_phase_cs``     -- ``Method.NoisyPhaseCS``: the same function on ``measurements_with_noisy_phase``
+                              (``scenario.ScenarioResult.y_noisy``).
 
 ``OMP.m`` is not in the reference tree (it belongs to the external CoSaMP_OMP toolbox); ``omp.py`` says what is
 implemented in its place.  With the reference's tolerance 1e-12 on noisy data OMP does not stop on the residual: it
@@ -140,6 +142,13 @@ def two_stage_batch(Phi, meas_sq, s, noise_power, *, tol=1e-12, max_atoms=None, 
     ts, sig = plomp_stage1(Phi, meas_sq, s, setup=setup, **pl_kw)
     kmax = ts.mCS if max_atoms is None else min(int(max_atoms), ts.mCS)
     return omp_batch(ts.C, sig, kmax, tol), _gamp_stage2(ts, sig, s, noise_power, Phi.shape[1])
+
+
+def noisy_phase_cs(Phi, y_noisy, s, *, solver="omp", noise_power=None):
+    """``Method.NoisyPhaseCS`` (Recover_Channel.m): ``My_Conventional_CS`` on ``measurements_with_noisy_phase``, the
+    coherent measurements with every entry multiplied by its own CN(0,1) draw (Generate_Measurement.m:102-103;
+    ``ScenarioResult.y_noisy``).  The recovery is ``perfect_phase_cs`` on that input, solver and limits included."""
+    return perfect_phase_cs(Phi, y_noisy, s, solver=solver, noise_power=noise_power)
 
 
 def perfect_phase_cs(Phi, y_complex, s, *, solver="omp", noise_power=None):

@@ -207,3 +207,137 @@ def multires_rows(seed, tx, M):
     lens, _ = multires_tiers(tx)
     tier = multires_tier_of(M, tx)
     return sum(lens[:tier]) + randperm(seed, 0x100, lens[tier], M).astype(np.int64), tier
+
+
+# ---- the reference's Monte-Carlo scenarios (host mirror of csrc/ace_scenario.hip) --------------------------------
+# Generate_Channel.m:64-142 and Generate_Measurement.m:67-118 on the counter streams above.  ``cfg`` is any object
+# with the fields of ``ace_scenario_cfg`` (``ScenarioCfg`` of ace_amd._lib; ``lambda`` is spelled ``lambda_``); None is
+# the default configuration, which is ``channel`` / ``measurements_complex`` / ``initial_iterate`` bit for bit.
+ST_NLOS_ANGLES, ST_NLOS_GAINS, ST_PHASE, ST_COMBINER = 10, 11, 12, 13
+
+
+class _ScenarioDefaults:
+    L, rician_k, on_grid, fix_angle, NQt, NQr, add_noise, noise_model = 3, 0, 0, 0, 0, 0, 1, 0
+    search_deg, k_factor_db, snr_db, x0_noise, ant_d, lambda_ = 95.0, 7.0, 30.0, 0.5, ANT_D, LAMBDA
+
+
+def _scfg(cfg):
+    cfg = _ScenarioDefaults if cfg is None else cfg
+    if not 1 <= cfg.L <= 8 or not 0 <= cfg.rician_k <= 16:
+        raise ValueError(f"L must be 1..8 and rician_k 0..16 (got {cfg.L}, {cfg.rician_k})")
+    if cfg.fix_angle and cfg.L != 1:
+        raise ValueError(f"fix_angle needs L == 1 (got L {cfg.L})")
+    if cfg.noise_model not in (0, 1):
+        raise ValueError(f"noise_model {cfg.noise_model} is neither 0 nor 1")
+    return cfg
+
+
+def scenario_grid(NQ):
+    """linspace(-1, 1, NQ + 1)(1:end-1) (Generate_Channel.m:83-86): the points p (2 / NQ) - 1, ``angular.grid_cut``'s."""
+    return np.linspace(-1.0, 1.0, int(NQ) + 1)[:-1]
+
+
+def _snap(s, NQ):
+    g = scenario_grid(NQ)
+    return g[np.argmin(np.abs(g[None, :] - s[:, None]), axis=1)]   # (argmin: the first on a tie, as MATLAB's min)
+
+
+def scenario_paths(seed, real, cfg=None, tx=None, rx=None):
+    """The draws of realisation ``real``: a dict with ``aod_deg``, ``aoa_deg`` [L], ``gains`` [L] (unit norm, before the
+    K-factor weights), ``nlos_aod``, ``nlos_aoa`` [Rk] (radians), ``nlos_gains`` [Rk], and ``flat``, the device's
+    ``paths`` row [4 (L + Rk)].  Rk = rician_k when L == 1, else 0.  tx, rx: the array sizes behind the default
+    grids NQ = 4 * antennas of on_grid (needed only when the cfg leaves NQt / NQr at 0)."""
+    cfg = _scfg(cfg)
+    L, Rk = int(cfg.L), (int(cfg.rician_k) if cfg.L == 1 else 0)
+    u = u01(seed, stream_id(ST_ANGLES, real), np.arange(2 * L, dtype=np.uint64))
+    aod, aoa = (u[:L] - 0.5) * cfg.search_deg, (u[L:] - 0.5) * cfg.search_deg
+    if cfg.fix_angle:
+        aod, aoa = np.array([0.0]), np.array([15.0])
+    if cfg.on_grid:
+        nqt, nqr = cfg.NQt or 4 * tx, cfg.NQr or 4 * rx
+        aod = np.arcsin(_snap(np.sin(aod * np.pi / 180.0), nqt)) * (180.0 / np.pi)
+        aoa = np.arcsin(_snap(np.sin(aoa * np.pi / 180.0), nqr)) * (180.0 / np.pi)
+    g = normal_pairs(seed, stream_id(ST_GAINS, real), L) * np.sqrt(0.5)
+    g = g / np.sqrt(np.sum(np.abs(g) ** 2))
+    un = u01(seed, stream_id(ST_NLOS_ANGLES, real), np.arange(2 * Rk, dtype=np.uint64))
+    naod, naoa = (un[:Rk] - 0.5) * np.pi, (un[Rk:] - 0.5) * np.pi
+    ng = normal_pairs(seed, stream_id(ST_NLOS_GAINS, real), Rk) * np.sqrt(0.5)
+    if Rk:
+        ng = ng / np.sqrt(np.sum(np.abs(ng) ** 2))
+    flat = np.concatenate([aod, aoa, g.view(np.float64), naod, naoa, ng.view(np.float64)])
+    return dict(aod_deg=aod, aoa_deg=aoa, gains=g, nlos_aod=naod, nlos_aoa=naoa, nlos_gains=ng, flat=flat)
+
+
+def k_factor_weights(cfg=None):
+    """(sqrt(K/(K+1)), sqrt(1/(K+1))) with K = 10^(k_factor_db/10) (Generate_Channel.m:132-135)."""
+    K = 10.0 ** (_scfg(cfg).k_factor_db / 10.0)
+    return np.sqrt(K / (K + 1.0)), np.sqrt(1.0 / (K + 1.0))
+
+
+def scenario_channel(seed, real, tx, rx, cfg=None):
+    """vecH (n = tx*rx, element r + rx*t = H[r][t]) at the reference's scale: the dominant paths, and with L == 1 and
+    rician_k > 0 the K-factor mix with the NLOS paths."""
+    cfg = _scfg(cfg)
+    p = scenario_paths(seed, real, cfg, tx, rx)
+    sd, sa, g = np.sin(p["aod_deg"] * np.pi / 180.0), np.sin(p["aoa_deg"] * np.pi / 180.0), p["gains"]
+    if p["nlos_gains"].size:
+        wd, wn = k_factor_weights(cfg)
+        sd, sa = np.concatenate([sd, np.sin(p["nlos_aod"])]), np.concatenate([sa, np.sin(p["nlos_aoa"])])
+        g = np.concatenate([wd * g, wn * p["nlos_gains"]])
+    kap = 2.0 * np.pi * (cfg.ant_d / cfg.lambda_)
+    k = np.arange(tx * rx)
+    r, t = k % rx, k // rx
+    ph = kap * (sd[None, :] * t[:, None] - sa[None, :] * r[:, None])
+    return np.sum(g[None, :] * (np.cos(ph) + 1j * np.sin(ph)), axis=1)
+
+
+def scenario_noise(seed, real, m, rx, cfg=None, W=None):
+    """The additive noise of the m probes: iid CN(0, sigma2) (model 0, ``measurements_complex``' draw), or
+    noise(it Mr + q) = sum_r conj(W[q][r]) N[r][q] with N[r][q] the stream-13 draw at counter q rx + r (model 1: the
+    reference's diag(W' * noiseMatrix), the same for every transmit beam); zeros with add_noise = 0."""
+    cfg = _scfg(cfg)
+    if not cfg.add_noise:
+        return np.zeros(m, np.complex128)
+    sigma2 = 10.0 ** (-cfg.snr_db / 10.0)
+    if cfg.noise_model == 0:
+        return normal_pairs(seed, stream_id(ST_NOISE, real), m) * np.sqrt(sigma2 * 0.5)
+    W = np.asarray(W, dtype=np.complex128)
+    Mr = W.shape[0]
+    if W.shape != (Mr, rx) or m % Mr:
+        raise ValueError(f"noise model 1 needs W [Mr][{rx}] with m % Mr == 0 (got {W.shape}, m {m})")
+    N = (normal_pairs(seed, stream_id(ST_COMBINER, real), Mr * rx) * np.sqrt(sigma2 * 0.5)).reshape(Mr, rx)   # [q][r]
+    return np.tile(np.sum(np.conj(W) * N, axis=1), m // Mr)
+
+
+def scenario_phase_noise(seed, real, m):
+    """The CN(0,1) factors of ``measurements_with_noisy_phase`` (stream 12, counter = probe)."""
+    return normal_pairs(seed, stream_id(ST_PHASE, real), m) * np.sqrt(0.5)
+
+
+def scenario_measurements(seed, real, A, vecH, rx, cfg=None, W=None):
+    """(y, y_noisy, B_raw, scale) of one realisation: y = A vecH + noise, y_noisy = y .* CN(0,1), B_raw = |y|."""
+    m = A.shape[0]
+    y = A @ vecH + scenario_noise(seed, real, m, rx, cfg, W)
+    B = np.abs(y)
+    return y, y * scenario_phase_noise(seed, real, m), B, np.sqrt(np.sum(B * B))
+
+
+def scenario(seed, first, count, m, tx, rx, A, cfg=None, W=None):
+    """Host copy of ``ace_synth_scenario``: a dict of the nine outputs for realisations first .. first + count - 1.
+    A: [m][n] or [1][m][n] (shared) or [count][m][n]."""
+    cfg = _scfg(cfg)
+    A = np.asarray(A, dtype=np.complex128)
+    A = A[None] if A.ndim == 2 else A
+    if A.shape[1:] != (m, tx * rx) or A.shape[0] not in (1, count):
+        raise ValueError(f"A must be [1 or {count}][{m}][{tx * rx}], got {A.shape}")
+    out = {k: [] for k in ("vecH", "y", "y_noisy", "B_raw", "scale", "B", "X0", "Hn", "paths")}
+    for c in range(count):
+        real = first + c
+        h = scenario_channel(seed, real, tx, rx, cfg)
+        y, yn, B, sc = scenario_measurements(seed, real, A[0 if A.shape[0] == 1 else c], h, rx, cfg, W)
+        x0 = initial_iterate(seed, real, h, cfg.x0_noise)
+        inv = 1.0 / sc if sc > 0 else 0.0
+        for k, v in (("vecH", h), ("y", y), ("y_noisy", yn), ("B_raw", B), ("scale", sc), ("B", B * inv),
+                     ("X0", x0 * inv), ("Hn", h * inv), ("paths", scenario_paths(seed, real, cfg, tx, rx)["flat"])):
+            out[k].append(v)
+    return {k: np.stack(v) if k != "scale" else np.asarray(v) for k, v in out.items()}

@@ -928,6 +928,58 @@ int ace_synth_channels(uint64_t seed, int64_t first, int count, int m, int tx, i
                        double snr_db, double x0_noise, const double* A, int a_shared,
                        double* vecH, double* B, double* X0, void* stream);
 
+/* ---- the reference's Monte-Carlo scenarios (Generate_Channel.m:64-142, Generate_Measurement.m:67-118) ----------
+ * ace_synth_scenario draws, for the realisations first .. first + count - 1, the channel and every measurement kind
+ * the programs under Numerical_Simulation/main_programs use, each at its own scale and without a host round trip:
+ *   channel  L dominant paths with AoD, AoA ~ U(-search_deg/2, search_deg/2) (fix_angle: 0 and 15 degrees), snapped
+ *            in sin to the grid linspace(-1,1,NQ+1)(1:end-1) with on_grid (nearest point, the first on a tie), unit-norm
+ *            CN gains; with L == 1, rician_k further paths with angles ~ U(-pi/2, pi/2) and unit-norm CN gains, mixed as
+ *            H = sqrt(K/(K+1)) H_dominant + sqrt(1/(K+1)) H_nlos, K = 10^(k_factor_db/10) (rician_k is ignored for
+ *            L > 1, as in the reference).  vecH [count][n] c128, n = tx rx, entry r + rx t = H[r][t].
+ *   measure  y = A vecH + noise; noise_model 0: iid CN(0, sigma2) per probe, sigma2 = 10^(-snr_db/10) (the model of
+ *            ace_synth_channels); noise_model 1: the reference's diag(W' * noiseMatrix) repeated per transmit beam,
+ *            noise(it Mr + q) = sum_r conj(W[q][r]) N[r][q], N iid CN(0, sigma2), W [Mr][rx] c128 the combiners as
+ *            ace_beam_scan_batch takes them (m = Mt Mr, probe i = it Mr + q).  add_noise = 0: y = A vecH (the
+ *            reference then reports noise_power 1e-10).  y_noisy = y .* CN(0,1) (measurements_with_noisy_phase),
+ *            B_raw = |y|, scale = ||B_raw||.
+ *   scaled   B = B_raw / scale, X0 = (vecH + x0_noise ||vecH|| / sqrt(n) CN(0,1)) / scale, Hn = vecH / scale: what
+ *            ace_synth_channels returns; zeros, not NaN, for a realisation with scale == 0.
+ *   paths    [count][4 (L + Rk)] f64, Rk = rician_k if L == 1 else 0: AoD [L] and AoA [L] in degrees, gains [2L]
+ *            (re, im; unit norm, before the K-factor weights), NLOS AoD [Rk] and AoA [Rk] in radians, NLOS gains [2Rk].
+ * Random streams (counter generator of ace_synth_*; kind + 16 (realisation + 1)): 2 angles, 3 gains, 4 iid noise
+ * (counter = probe), 5 X0 -- so the default cfg draws ace_synth_channels' numbers -- and 10 NLOS angles, 11 NLOS gains,
+ * 12 phase noise (counter = probe), 13 combiner noise matrix (counter = q rx + r).
+ * All pointers are DEVICE pointers; A is [a_shared ? 1 : count][m][n] c128; every output may be NULL and the others do
+ * not depend on which are.  A realisation's outputs are a function of (cfg, seed, its index, A, W) alone: not of
+ * count or of its place in the call.  With a shared A the product runs on the f64 matrix cores over the whole call
+ * (csrc/ace_scenario.hip); no atomics, every sum has a fixed order.  Asynchronous on `stream`, reads nothing back, can
+ * be captured.  workspace: ace_synth_scenario_workspace_size(...) bytes of DEVICE memory (0 outside the limits);
+ * ACE_ERR_WORKSPACE when NULL or shorter.
+ * Limits: 1 <= tx, rx <= 32, 1 <= m <= 4096, 1 <= L <= 8, 0 <= rician_k <= 16, 0 <= NQt, NQr <= 65536
+ * (ACE_ERR_UNSUPPORTED above, ACE_ERR_ARG below); count < 1, first < 0, fix_angle with L > 1, a noise_model other than
+ * 0 / 1, noise_model 1 without W or with Mr < 1 or m % Mr != 0, a search_deg outside (0, 180], a non-finite snr_db or
+ * k_factor_db, x0_noise < 0, ant_d or lambda not positive and finite, and a NULL cfg or A return ACE_ERR_ARG; all of it
+ * before any HIP call. */
+typedef struct ace_scenario_cfg {
+    int L;              /* dominant paths, 1..8 */
+    int rician_k;       /* NLOS paths; used only when L == 1 (Generate_Channel.m: forced to 0 for L > 1), 0..16 */
+    int on_grid;        /* snap the dominant AoD/AoA to linspace(-1,1,NQ+1)(1:end-1) in sin, first on a tie */
+    int fix_angle;      /* AoD = 0, AoA = 15 deg; needs L == 1 */
+    int NQt, NQr;       /* grid sizes for on_grid; 0 = 4 * antennas */
+    int add_noise;      /* 0: y = A h, reported noise_power 1e-10 (Add_Noise_Flag = 0) */
+    int noise_model;    /* 0 iid CN(0, sigma2) per probe (the synth's); 1 the reference's W' * noiseMatrix */
+    double search_deg;  /* Searching_Area: AoD, AoA ~ U(-search_deg/2, search_deg/2) */
+    double k_factor_db; /* 7 */
+    double snr_db, x0_noise, ant_d, lambda;
+} ace_scenario_cfg;
+void ace_scenario_cfg_default(ace_scenario_cfg* cfg);   /* L 3, rician_k 0, 95 deg, iid, 30 dB, 0.5: ace_synth_channels' scenario */
+size_t ace_synth_scenario_workspace_size(const ace_scenario_cfg* cfg, int count, int m, int tx, int rx, int Mr);
+int ace_synth_scenario(const ace_scenario_cfg* cfg, uint64_t seed, int64_t first, int count, int m, int tx, int rx,
+                       const double* A, int a_shared, const double* W, int Mr,
+                       double* vecH, double* y, double* y_noisy, double* B_raw, double* scale,
+                       double* B, double* X0, double* Hn, double* paths,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- kernel timing (measurement only; no reference counterpart) ----------------
  * Between ace_prof_start and ace_prof_stop every kernel ace_admm_solve_batch
  * enqueues is bracketed by a pair of hipEvents recorded on the launch stream.
