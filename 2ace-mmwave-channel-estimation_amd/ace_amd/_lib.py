@@ -177,6 +177,17 @@ class NmsArgs(C.Structure):
                 + [(k, _ip) for k in ("flags_out", "done_count_out", "guard_ok")])
 
 
+class PcArgs(C.Structure):
+    """Mirror of ``ace_pc_args`` (include/ace.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("op", "form", "batch", "m", "n", "yn_id", "guard", "reserved")]
+                + [("sentinel", C.c_double)]
+                + [(k, _dp) for k in ("A", "Gin", "X0", "G", "B", "Yo", "M", "AX", "Yn", "optY", "Z", "N", "state")]
+                + [("flags", _ip), ("cb", _dp), ("codes", C.POINTER(C.c_uint32))]
+                + [(k, _dp) for k in ("Gw", "Gt", "P0", "B_out", "Yo_out", "M_out", "AX_out", "Yn_out", "optY_out", "W",
+                                      "Z_out", "N_out", "state_out")]
+                + [(k, _ip) for k in ("flag_out", "flags_out", "guard_ok")])
+
+
 def _load():
     if not LIB_PATH.exists():
         raise ImportError(
@@ -304,6 +315,8 @@ def _load():
     lib.ace_stage_host.restype = C.c_int
     lib.ace_nms_host.argtypes = [C.POINTER(NmsArgs)]
     lib.ace_nms_host.restype = C.c_int
+    lib.ace_pc_host.argtypes = [C.POINTER(PcArgs)]
+    lib.ace_pc_host.restype = C.c_int
     lib.ace_last_error.argtypes = []
     lib.ace_last_error.restype = C.c_char_p
     lib.ace_version.argtypes = []

@@ -454,6 +454,14 @@ void launch_pc_pack(int batch, int m, int n, const double* A, double* cb, uint32
 // Gw <- I + A A^H (exact from the codes), inverted in place; Gt <- its lower tiles
 void launch_pc_ginv(int batch, int m, int n, const uint32_t* codes, const double* cb, double* Gw, double* Gt,
                     hipStream_t st);
+// The three steps of launch_pc_ginv on their own (the test entry ace_pc_host runs them one at a time): I + K from
+// the row-major codes cR; the in-place inverse of [batch][mp32][mp32] Hermitian positive definite matrices by the
+// Schur recursion (its scratch follows the batch's matrices in Gw: pc_gw_bytes) or the blocked Gauss-Jordan; the
+// lower tiles.
+enum { PC_INV_SCHUR = 0, PC_INV_GJ = 1 };
+void launch_pc_k(int batch, int m, int n, const uint32_t* cR, const double* cb, double* Gw, hipStream_t st);
+void launch_pc_inv(int batch, int m, double* Gw, int form, hipStream_t st);
+void launch_pc_tiles(int batch, int m, const double* Gw, double* Gt, hipStream_t st);
 struct PgkArgs {
     int m, n;
     const uint32_t* codesH;   // A^H images of the batch (launch_pc_pack)

@@ -925,23 +925,43 @@ static bool pc_use_gj() {   // ACE_PC_GJ=1: the blocked Gauss-Jordan of r01 (A/B
     return v;
 }
 
-void launch_pc_ginv(int batch, int m, int n, const uint32_t* codes, const double* cb, double* Gw, double* Gt,
-                    hipStream_t st) {
-    if (!pc_use_gj()) {
-        const PcDims d = pc_dims(m, n);
-        const uint32_t* cR = codes + (size_t)batch * d.nctH * d.nkgH * 128 + (size_t)batch * d.nctA * d.nkgA * 128;
+void launch_pc_k(int batch, int m, int n, const uint32_t* cR, const double* cb, double* Gw, hipStream_t st) {
+    const PcDims d = pc_dims(m, n);
+    hipLaunchKernelGGL(pc_k_kernel, dim3(batch, d.nb32 * (d.nb32 + 1) / 2), dim3(PNT), (size_t)64 * (d.nwR + 1) * 4, st,
+                       m, n, cR, cb, Gw);
+}
+
+void launch_pc_inv(int batch, int m, double* Gw, int form, hipStream_t st) {
+    const PcDims d = pc_dims(m, 16);
+    if (form == PC_INV_SCHUR) {
         const long long s2 = (long long)d.mp32 * d.mp32;   // complex elements per matrix
         // matrices [batch][mp32][mp32], then the scratch [batch][pc_inv_scratch]
         double* scr = Gw + 2 * s2 * batch;
         const long long ss = std::max(1LL, pc_inv_scratch(d.mp32));
-        hipLaunchKernelGGL(pc_k_kernel, dim3(batch, d.nb32 * (d.nb32 + 1) / 2), dim3(PNT), (size_t)64 * (d.nwR + 1) * 4,
-                           st, m, n, cR, cb, Gw);
         pc_inv_rec(batch, d.mp32, Gw, d.mp32, s2, scr, ss, st);
-        hipLaunchKernelGGL(pc_tiles_kernel, dim3(batch, d.ntile), dim3(PNT), 0, st, m, Gw, Gt);
         return;
     }
+    for (int k = 0; k < d.nb32; ++k) {
+        hipLaunchKernelGGL(gj_panel_kernel, dim3(batch), dim3(PNT), 0, st, d.mp32, k, Gw);
+        if (d.nb32 > 1) hipLaunchKernelGGL(gj_update_kernel, dim3(batch, d.nb32 - 1), dim3(PNT), 0, st, d.mp32, k, Gw);
+    }
+}
+
+void launch_pc_tiles(int batch, int m, const double* Gw, double* Gt, hipStream_t st) {
+    const PcDims d = pc_dims(m, 16);
+    hipLaunchKernelGGL(pc_tiles_kernel, dim3(batch, d.ntile), dim3(PNT), 0, st, m, Gw, Gt);
+}
+
+void launch_pc_ginv(int batch, int m, int n, const uint32_t* codes, const double* cb, double* Gw, double* Gt,
+                    hipStream_t st) {
     const PcDims d = pc_dims(m, n);
     const uint32_t* cR = codes + (size_t)batch * d.nctH * d.nkgH * 128 + (size_t)batch * d.nctA * d.nkgA * 128;
+    if (!pc_use_gj()) {
+        launch_pc_k(batch, m, n, cR, cb, Gw, st);
+        launch_pc_inv(batch, m, Gw, PC_INV_SCHUR, st);
+        launch_pc_tiles(batch, m, Gw, Gt, st);
+        return;
+    }
     static const int chunk_env = [] {
         const char* e = exp_env("ACE_PC_CHUNK");
         return e ? atoi(e) : 0;
@@ -951,13 +971,9 @@ void launch_pc_ginv(int batch, int m, int n, const uint32_t* codes, const double
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         double* Gwc = Gw + gws * b0;
-        hipLaunchKernelGGL(pc_k_kernel, dim3(nb, d.nb32 * (d.nb32 + 1) / 2), dim3(PNT), (size_t)64 * (d.nwR + 1) * 4,
-                           st, m, n, cR + (size_t)b0 * m * d.nwR, cb + b0, Gwc);
-        for (int k = 0; k < d.nb32; ++k) {
-            hipLaunchKernelGGL(gj_panel_kernel, dim3(nb), dim3(PNT), 0, st, d.mp32, k, Gwc);
-            if (d.nb32 > 1) hipLaunchKernelGGL(gj_update_kernel, dim3(nb, d.nb32 - 1), dim3(PNT), 0, st, d.mp32, k, Gwc);
-        }
-        hipLaunchKernelGGL(pc_tiles_kernel, dim3(nb, d.ntile), dim3(PNT), 0, st, m, Gwc, Gt + gts * b0);
+        launch_pc_k(nb, m, n, cR + (size_t)b0 * m * d.nwR, cb + b0, Gwc, st);
+        launch_pc_inv(nb, m, Gwc, PC_INV_GJ, st);
+        launch_pc_tiles(nb, m, Gwc, Gt + gts * b0, st);
     }
 }
 

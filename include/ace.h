@@ -40,6 +40,8 @@
  *                            rescale :93-107, the per-realisation partitions' Schur form) on host arrays.
  *  ace_nms_host           <- test entry: one operation of the A2nuclear m-space iteration (init, one
  *                            iteration, the pending convergence tests, the output parts) on host arrays.
+ *  ace_pc_host            <- test entry: one operation of the private code-image kernels (code images, I + K,
+ *                            the inverse, the tiles, A X0, one iteration launch) on host arrays.
  *
  * Conventions
  *  - Complex values are complex128, interleaved (re, im) doubles.
@@ -277,7 +279,8 @@ int ace_prox_eig_host(int batch, int d, int path, const double* A, const double*
  * flags (NULL: 0) and AX (int8 apply_A at rcols = 1 only: the A V of realisations with avok) are optional.
  * out ([batch * rcols][m], AH: [..][n]) is filled with `sentinel` before the launch, so rows a kernel leaves
  * alone (done realisations) show.  The fused kernels that carry solver state (the g / Y-step / K Y kernels, the
- * private code-image kernel, apply_AH's fused Z-step) are not reachable from here.
+ * apply_AH's fused Z-step) are not reachable from here; the private code-image kernels (pgk_kernel and their setup)
+ * are reachable one launch at a time through ace_pc_host below.
  * Synchronous; allocates its own device memory. */
 #define ACE_LINOP_A 0
 #define ACE_LINOP_AH 1
@@ -472,6 +475,52 @@ typedef struct ace_nms_args {
     int32_t *flags_out, *done_count_out, *guard_ok;
 } ace_nms_args;
 int ace_nms_host(const ace_nms_args* args);
+
+/* ---- test entry: one operation of the private code-image kernels (csrc/ace_private.hip) on host arrays --------
+ * The setup and iteration kernels of the private phase-code path (one codebook per realisation) on their own
+ * (tests/test_gpu_pc.py compares them with the references of tests/pc_ref.py).  Every operation calls the launchers
+ * a solve calls; launch_pc_ginv's three steps are reachable one at a time:
+ *   ACE_PC_PACK     A [b][m][n] -> cb [b], flag_out [1], codes (the A^H, A and row-major images of the batch, one
+ *                   after the other as the launcher lays them out: b nH, b nA, b nR dwords)
+ *   ACE_PC_KMAT     A (packed first) -> Gw [b][mp32][mp32] = I + K (pc_k_kernel alone)
+ *   ACE_PC_INV      Gin [b][mp32][mp32] Hermitian positive definite, form (ACE_PC_SCHUR / ACE_PC_GJ) -> Gw, the
+ *                   inverse in place (the inverse launcher alone)
+ *   ACE_PC_TILES    Gin [b][mp32][mp32] -> Gt [b][ntile][16][16] (pc_tiles_kernel alone)
+ *   ACE_PC_APPLY_A  A (packed first), X0 [b][n] -> P0 [b][m]
+ *   ACE_PC_STEP     one pgk_kernel launch: A (packed first); G [b][m][m] (NULL: the setup's own G_b through
+ *                   launch_pc_ginv; given: through pc_tiles_kernel, only its lower 16 x 16 tiles are read); B [b][m]
+ *                   doubles, Yo, M [b][m], Z, N [b][n], state, flags; AX, Yn, optY [b][m] optional (NULL: sentinel);
+ *                   yn_id 0 (opt_Y copied at once) or 1 / 2 (deferred, RealState::optysrc)
+ *                   -> AX_out, M_out, Yn_out, W [b][n], optY_out, state_out, flags_out, Gt, and the arrays the
+ *                   kernel must not write (B_out, Yo_out, Z_out, N_out)
+ * mp32 = 32 ceil(m / 32), ntile = mt (mt + 1) / 2 with mt = ceil(m / 16); with nct = ceil(n / 16):
+ * nH = nct ceil(mt / 8) 128, nA = mt ceil(nct / 8) 128, nR = m nct.
+ * All arrays are HOST; c128 as (re, im) doubles.  Every device buffer a kernel writes starts from `sentinel` (the code
+ * images: from 0xFF bytes) and is followed by `guard` doubles (dwords) of it: an output array has its rows and then
+ * the guard (codes: one guard after the three images; Gw: the guard that follows the recursion's scratch).  Outputs
+ * may be NULL.
+ *   state, state_out [batch][ACE_PC_NSTATE]: mu, opt_obj, vbound, obj2, nAX2, nY2, nJM2, dY2, dAtY, nAtY
+ *   flags, flags_out [batch][ACE_PC_NFLAG]: done, avok, nzero, optysrc
+ *   guard_ok: 1 when the control block after the batch's and every control-block field not listed above are as
+ *          they were
+ * Checked before any HIP call: ACE_ERR_ARG for an unknown op or form, batch, m or n < 1, a negative guard, yn_id
+ * outside 0..2, mu <= 0 (step) and a NULL required array (named in ace_last_error()); ACE_ERR_UNSUPPORTED for
+ * m > 256, n > 2048 and for an LDS request beyond pc_supported.  Synchronous; allocates its own device memory. */
+enum { ACE_PC_PACK = 0, ACE_PC_KMAT, ACE_PC_INV, ACE_PC_TILES, ACE_PC_APPLY_A, ACE_PC_STEP, ACE_PC_NOPS };
+enum { ACE_PC_SCHUR = 0, ACE_PC_GJ, ACE_PC_NFORMS };
+#define ACE_PC_NSTATE 10
+#define ACE_PC_NFLAG 4
+typedef struct ace_pc_args {
+    int32_t op, form, batch, m, n, yn_id, guard, reserved;
+    double sentinel;
+    const double *A, *Gin, *X0, *G, *B, *Yo, *M, *AX, *Yn, *optY, *Z, *N, *state;
+    const int32_t* flags;
+    double* cb;
+    uint32_t* codes;
+    double *Gw, *Gt, *P0, *B_out, *Yo_out, *M_out, *AX_out, *Yn_out, *optY_out, *W, *Z_out, *N_out, *state_out;
+    int32_t *flag_out, *flags_out, *guard_ok;
+} ace_pc_args;
+int ace_pc_host(const ace_pc_args* args);
 
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(

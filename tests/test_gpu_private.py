@@ -48,7 +48,9 @@ def _launches(fn):
     return dict(zip(KERNEL_CLASSES, kn))
 
 
-@pytest.mark.parametrize("tx,m", [(16, 64), (16, 20), (16, 48), (16, 160), (32, 256)])
+# (6, 20) and (10, 48): n = tx^2 = 36 and 100 are no multiples of 16 (the n tails of the code images, of the A^H
+# epilogue and of the row-major codes; tests/test_gpu_pc.py has them one launch at a time)
+@pytest.mark.parametrize("tx,m", [(16, 64), (16, 20), (16, 48), (16, 160), (32, 256), (6, 20), (10, 48)])
 @pytest.mark.parametrize("fixed", [True, False])
 def test_private_phase_code_matches_oracle(gpu, tx, m, fixed):
     from ace_amd import infer_admm_host
