@@ -188,6 +188,23 @@ class PcArgs(C.Structure):
                 + [(k, _ip) for k in ("flag_out", "flags_out", "guard_ok")])
 
 
+PL_F64 = ("x", "xo", "z", "zo", "y", "G", "Znew", "P", "VT", "V", "Ax", "Axo", "Az", "Azo", "Ay", "gAy", "gAx", "Aex",
+          "bvec", "R", "RT", "Pg", "T", "tau", "C", "lam", "misc", "K", "cholR", "V1", "w")
+PL_I32 = ("act", "cnt", "ok", "iters", "status")
+
+
+class PlArgs(C.Structure):
+    """Mirror of ``ace_pl_args`` (include/ace.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("op", "batch", "m", "d", "guard", "reduced", "cntr_reset", "restart",
+                                          "maxIts", "reserved")]
+                + [(k, C.c_double) for k in ("lambda", "alpha", "beta", "Lexact", "tol", "L0", "sentinel")]
+                + [(k, _dp) for k in PL_F64 + ("state",)]
+                + [(k, _ip) for k in PL_I32]
+                + [(k + "_out", _dp) for k in PL_F64 + ("state",)]
+                + [(k + "_out", _ip) for k in PL_I32]
+                + [("guard_ok", _ip)])
+
+
 def _load():
     if not LIB_PATH.exists():
         raise ImportError(
@@ -317,6 +334,8 @@ def _load():
     lib.ace_nms_host.restype = C.c_int
     lib.ace_pc_host.argtypes = [C.POINTER(PcArgs)]
     lib.ace_pc_host.restype = C.c_int
+    lib.ace_pl_host.argtypes = [C.POINTER(PlArgs)]
+    lib.ace_pl_host.restype = C.c_int
     lib.ace_last_error.argtypes = []
     lib.ace_last_error.restype = C.c_char_p
     lib.ace_version.argtypes = []

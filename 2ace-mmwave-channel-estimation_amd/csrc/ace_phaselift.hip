@@ -551,7 +551,9 @@ __global__ __launch_bounds__(256) void chol_kernel(int m, const double* Kp, doub
         if (t == 0) {
             const double djj = R[(long long)j * m + j].x;
             if (!(djj > 0.0)) bad = 1;
-            piv = sqrt(fmax(djj, 1e-300));
+            // (a non-positive pivot is replaced by 1: a 1e-150 pivot scales its row by 1e150 and the rows after it
+            // overflow; K is then not positive definite, ok = 0 and R is not used, but it stays finite)
+            piv = djj > 0.0 ? sqrt(fmax(djj, 1e-300)) : 1.0;
         }
         __syncthreads();
         const double inv = 1.0 / piv;

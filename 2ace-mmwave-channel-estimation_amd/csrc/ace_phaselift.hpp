@@ -53,6 +53,10 @@ void launch_pl_iterate(const PlArgs& a, hipStream_t st);
 // a[b][i] = Re sum_r conj(R[r][i]) T[b][r][i]  (A(X) = diag(R^H X R) from T = X R)
 void launch_pl_diagform(int d, int m, int batch, const double* R, const double* T, double* out, const int* act,
                         hipStream_t st);
+// the solve's GEMM steps (ace_phaselift_host.cpp): A(X) into out, g_y = A*(g_Ay) into a.G, the prox assembly into a.Znew
+void pl_apply_A(const PlArgs& a, const double* RT, double* T, const double* X, double* out, hipStream_t st);
+void pl_g_y(const PlArgs& a, hipStream_t st);
+void pl_zasm(const PlArgs& a, hipStream_t st);
 void launch_pl_outputs(int batch, const PlState* st, int32_t* iters, uint32_t* status, hipStream_t s);
 void launch_chol(int m, const double* K, double* R, int* ok, hipStream_t st);
 void launch_ztranspose(int rows, int cols, const double* S, double* D, hipStream_t st);

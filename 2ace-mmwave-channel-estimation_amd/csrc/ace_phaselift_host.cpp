@@ -46,6 +46,28 @@ void pl_carve(Carver& cv, const PlDims& D, PlWs* w) {
     a.scratch = cv.take(heev_scratch_bytes(D.d, D.d, D.batch));
 }
 
+}  // namespace
+
+namespace ace {
+// The three GEMM steps of the inner iteration, shared with the test entry (ace_pl_host.cpp).
+// out = A(X) = diag(R^H X R), active rows only: T = X R by the RT GEMM, then pl_diagform_kernel
+void pl_apply_A(const PlArgs& a, const double* RT, double* T, const double* X, double* out, hipStream_t st) {
+    launch_zgemm(0, false, a.m, a.d, a.batch * a.d, RT, a.d, 0, X, a.d, 0, T, nullptr, a.m, 0, 1, st);
+    launch_pl_diagform(a.d, a.m, a.batch, a.R, T, out, a.act, st);
+}
+// g_y = A*(g_Ay) = R diag(g) R^H from Pg = R o g
+void pl_g_y(const PlArgs& a, hipStream_t st) {
+    launch_zgemm(0, true, a.d, a.m, a.batch * a.d, a.R, a.m, 0, a.Pg, a.m, 0, a.G, nullptr, a.d, 0, 1, st);
+}
+// Znew = V diag(s) V^H (summation over the kept pairs only: P's and VT's columns q >= k are zero, misc[0] = k)
+void pl_zasm(const PlArgs& a, hipStream_t st) {
+    const int d = a.d;
+    launch_zgemm(0, true, d, d, d, a.VT, d, (long long)d * d, a.P, d, (long long)d * d, a.Znew, nullptr, d,
+                 (long long)d * d, a.batch, st, a.scratch + a.hl.misc, a.hl.stride);
+}
+}  // namespace ace
+
+namespace {
 int validate(const ace_phaselift_cfg* c, int batch, int m, int n, PlDims* D) {
     if (!c) return fail(ACE_ERR_ARG, "cfg is NULL");
     if (batch < 1 || m < 1 || n < 1) return fail(ACE_ERR_ARG, "batch/m/n must be >= 1 (got %d/%d/%d)", batch, m, n);
@@ -152,10 +174,7 @@ int solve_batch(const ace_phaselift_cfg* cfg, int batch, int m, int n, const dou
     launch_pl_init(a, st);
     ACE_LAUNCHED("PhaseLift init");
 
-    auto applyA = [&](const double* X, double* out) {  // out = A(X) = diag(R^H X R), active rows only
-        launch_zgemm(0, false, m, d, batch * d, w.RT, d, 0, X, d, 0, w.T, nullptr, m, 0, 1, st);
-        launch_pl_diagform(d, m, batch, a.R, w.T, out, a.act, st);
-    };
+    auto applyA = [&](const double* X, double* out) { pl_apply_A(a, w.RT, w.T, X, out, st); };
     // the prox's reduction (launch_heev's path): the two-stage one (ace_heev2.hip, r06) where it applies, else the
     // panel-blocked one-stage hetrd_blk_kernel; ACE_HETRD_BLK=0 / 1 / 2 selects the unblocked / blocked one-stage /
     // two-stage reduction (A/B and the GPU tests that pin the paths against each other), read once per solve
@@ -188,7 +207,7 @@ int solve_batch(const ace_phaselift_cfg* cfg, int batch, int m, int n, const dou
             const double act = h[0], dd3 = (double)d * d * d, dd2m = (double)d * d * m;
             if (h[4]) {  // g_y = A*(g_Ay) = R diag(g) R^H
                 ProfScope ps(ACE_K_APPLY_AH, st, 8.0 * dd2m * act);
-                launch_zgemm(0, true, d, m, batch * d, a.R, m, 0, a.Pg, m, 0, a.G, nullptr, d, 0, 1, st);
+                pl_g_y(a, st);
             }
             {
                 ProfScope ps(ACE_K_ZSTEP, st, 17.3 * dd3 * act);   // prox_trace: eig of z_old - step g_y, shrink
@@ -198,9 +217,7 @@ int solve_batch(const ace_phaselift_cfg* cfg, int batch, int m, int n, const dou
             }
             {
                 ProfScope ps(ACE_K_APPLY_G, st, 8.0 * dd3 * act);   // z = V diag(s) V^H
-                // (summation over the kept pairs only: P's and VT's columns q >= k are zero, misc[0] = k)
-                launch_zgemm(0, true, d, d, d, a.VT, d, (long long)d * d, a.P, d, (long long)d * d, a.Znew, nullptr, d,
-                             (long long)d * d, batch, st, a.scratch + a.hl.misc, a.hl.stride);
+                pl_zasm(a, st);
                 launch_pl_take_z(a, st);
             }
             { ProfScope ps(ACE_K_APPLY_A, st, 8.0 * dd2m * act); applyA(a.z, a.Az); }

@@ -42,6 +42,8 @@
  *                            iteration, the pending convergence tests, the output parts) on host arrays.
  *  ace_pc_host            <- test entry: one operation of the private code-image kernels (code images, I + K,
  *                            the inverse, the tiles, A X0, one iteration launch) on host arrays.
+ *  ace_pl_host            <- test entry: one operation of the PhaseLift step kernels (each step of the TFOCS
+ *                            iteration, its GEMMs, the Cholesky setup, the final vector) on host arrays.
  *
  * Conventions
  *  - Complex values are complex128, interleaved (re, im) doubles.
@@ -521,6 +523,67 @@ typedef struct ace_pc_args {
     int32_t *flag_out, *flags_out, *guard_ok;
 } ace_pc_args;
 int ace_pc_host(const ace_pc_args* args);
+
+/* ---- test entry: one operation of the PhaseLift step kernels (csrc/ace_phaselift.hip) on host arrays ------------
+ * The kernels of the TFOCS Auslender-Teboulle iteration of MyPhaseLift, its setup and its output on their own
+ * (tests/test_gpu_pl.py compares them with the restatements of tests/pl_ref.py).  Every operation calls the launcher
+ * the solve calls (launch_pl_*, launch_chol, launch_ztranspose, and launch_zgemm through the solve's own pl_apply_A /
+ * pl_g_y / pl_zasm):
+ *   ACE_PL_INIT         pl_init_kernel: bvec -> gAy, gAx, state
+ *   ACE_PL_OUTER_BEGIN  pl_outer_begin_kernel: x, z, Ax, Az, state -> xo, zo, Axo, Azo, state
+ *   ACE_PL_THETA        pl_theta_kernel: state, cnt -> state, act, cnt
+ *   ACE_PL_MAKE_Y       pl_make_y_kernel: xo, zo, state, act -> y
+ *   ACE_PL_SET_AY       pl_set_Ay_kernel: Axo, Azo, Aex, state, act -> Ay
+ *   ACE_PL_GRAD         pl_grad_kernel: Ay, bvec, gAy, R, state, act -> gAy, Pg, tau, state
+ *   ACE_PL_GY           the solve's GEMM G = R diag(g) R^H: R, Pg -> G
+ *   ACE_PL_PROX_IN      pl_prox_in_kernel: zo, G, state, act -> C
+ *   ACE_PL_ASSEMBLE     pl_assemble_kernel: V, lam, misc, tau, state, act -> P, VT, state
+ *   ACE_PL_ZASM         the solve's batched klim GEMM: VT, P, misc -> Znew
+ *   ACE_PL_TAKE_Z       pl_take_z_kernel: Znew, zo, G, misc, tau, state, act -> z
+ *   ACE_PL_APPLY_A      the solve's A(x): the RT GEMM, then pl_diagform_kernel: x, R, RT, act -> T, Aex
+ *   ACE_PL_MAKE_X       pl_make_x_kernel: xo, z, y, G, Axo, Az, state, act, cnt -> x, Ax, state, cnt
+ *   ACE_PL_SET_AX       pl_set_Ax_kernel: Aex, state, act -> Ax
+ *   ACE_PL_BACKTRACK    pl_backtrack_kernel: Ax, Ay, bvec, gAy, state, act -> gAx, state
+ *   ACE_PL_ITERATE      pl_iterate_kernel: x, Ax, gAx, state, cnt -> y, z, Ay, Az, gAy, state, cnt
+ *   ACE_PL_CHOL         chol_kernel: K [m][m] -> cholR [m][m], ok [1]
+ *   ACE_PL_TRANSPOSE    ztranspose_kernel: R [d][m] -> RT [m][d]
+ *   ACE_PL_FINAL_VEC    pl_final_in_kernel, then pl_final_vec_kernel: x, V1 [b][d], lam (lam[b][0] is read), `reduced`
+ *                       (1: R [d][d] upper triangular, m == d) -> C, w [b][d]
+ *   ACE_PL_OUTPUTS      pl_outputs_kernel: state, status -> iters, status
+ * Shapes (HOST arrays; c128 as (re, im) doubles): x, xo, z, zo, y, G, Znew, P, VT, V, C [b][d][d] c128; Ax, Axo, Az,
+ * Azo, Ay, gAy, gAx, Aex, bvec [b][m] f64; R [d][m], RT [m][d] c128; Pg, T [b][d][m] c128; tau [b]; lam [b][d];
+ * misc [b][3]; K, cholR [m][m] c128; V1, w [b][d] c128; act, iters, status [b], cnt [9], ok [1] int32.  C, lam and misc
+ * are the eigensolver's slots of the scratch, at heev_layout(d, d) offsets (FINAL_VEC: heev_layout(d, 1)).
+ * An input that is NULL starts from `sentinel` (int32: from ACE_PL_ISENTINEL); every buffer is followed by `guard`
+ * doubles (ints) of it and comes back, guard included, in its `_out` array (count + guard elements; may be NULL).
+ *   state, state_out [batch][ACE_PL_NSTATE]: L, L_old, theta, theta_old, f_x, f_y, C_x, C_z, cntr_Ax, cntr_Ay, xy_sq,
+ *          nx2, ndx2, dot_xy_g, localL, step, n_iter, restart_iter, backtrack_simple, backtrack_steps, have_gAy,
+ *          have_gy, have_gAx, ycomp, need_Ay, need_Ax, inner, done, status
+ *          (PlState in field order; the int32 fields as exact doubles, Inf and NaN carried through)
+ *   guard_ok: 1 when every guard, every buffer the operation does not write (the rest of the scratch and the state's
+ *          padding included) and the state block after the batch's are bit for bit as they were
+ * Checked before any HIP call: ACE_ERR_ARG for an unknown op, batch, m or d < 1, a negative guard, reduced with
+ * m != d (FINAL_VEC) and a NULL required array (named in ace_last_error()); ACE_ERR_UNSUPPORTED for d > 1600.
+ * Synchronous; allocates its own device memory. */
+enum {
+    ACE_PL_INIT = 0, ACE_PL_OUTER_BEGIN, ACE_PL_THETA, ACE_PL_MAKE_Y, ACE_PL_SET_AY, ACE_PL_GRAD, ACE_PL_GY,
+    ACE_PL_PROX_IN, ACE_PL_ASSEMBLE, ACE_PL_ZASM, ACE_PL_TAKE_Z, ACE_PL_APPLY_A, ACE_PL_MAKE_X, ACE_PL_SET_AX,
+    ACE_PL_BACKTRACK, ACE_PL_ITERATE, ACE_PL_CHOL, ACE_PL_TRANSPOSE, ACE_PL_FINAL_VEC, ACE_PL_OUTPUTS, ACE_PL_NOPS
+};
+#define ACE_PL_NSTATE 29
+#define ACE_PL_ISENTINEL 0x5A5A5A5A
+typedef struct ace_pl_args {
+    int32_t op, batch, m, d, guard, reduced, cntr_reset, restart, maxIts, reserved;
+    double lambda, alpha, beta, Lexact, tol, L0, sentinel;
+    const double *x, *xo, *z, *zo, *y, *G, *Znew, *P, *VT, *V, *Ax, *Axo, *Az, *Azo, *Ay, *gAy, *gAx, *Aex, *bvec, *R, *RT;
+    const double *Pg, *T, *tau, *C, *lam, *misc, *K, *cholR, *V1, *w, *state;
+    const int32_t *act, *cnt, *ok, *iters, *status;
+    double *x_out, *xo_out, *z_out, *zo_out, *y_out, *G_out, *Znew_out, *P_out, *VT_out, *V_out, *Ax_out, *Axo_out;
+    double *Az_out, *Azo_out, *Ay_out, *gAy_out, *gAx_out, *Aex_out, *bvec_out, *R_out, *RT_out, *Pg_out, *T_out;
+    double *tau_out, *C_out, *lam_out, *misc_out, *K_out, *cholR_out, *V1_out, *w_out, *state_out;
+    int32_t *act_out, *cnt_out, *ok_out, *iters_out, *status_out, *guard_ok;
+} ace_pl_args;
+int ace_pl_host(const ace_pl_args* args);
 
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(
