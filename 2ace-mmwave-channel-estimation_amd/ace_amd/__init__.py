@@ -28,7 +28,7 @@ from ._lib import ACE_ST_EVAL_DEGENERATE, ACE_ST_OMP_DEPENDENT  # noqa: F401
 from ._lib import ACE_ST_GAMP_NANBREAK, ACE_ST_GAMP_MAXEM, ACE_ST_GAMP_FAILED, GampCfg, gamp_cfg  # noqa: F401
 from ._lib import ACE_ST_PRGAMP_FAILED, ACE_ST_PRGAMP_MAXTRY, PrGampCfg, prgamp_cfg  # noqa: F401
 from . import synth, engine, montecarlo, linops, zprox, realtrace, scan, angular, omp, gamp, prgamp, sparse, minl2  # noqa: F401
-from . import stages, nms, pcode, plstep  # noqa: F401
+from . import stages, nms, pcode, plstep, ustep  # noqa: F401
 from .design import aopt_select_batch, aopt_select_host, bayes_beam, AoptResult  # noqa: F401
 from ._lib import ACE_ST_AOPT_SINGULAR, AoptCfg, aopt_cfg  # noqa: F401
 from . import design  # noqa: F401

@@ -205,6 +205,25 @@ class PlArgs(C.Structure):
                 + [("guard_ok", _ip)])
 
 
+UNIT_VM = ("T", "g", "Y0", "Y1", "KY0", "KY1", "M", "AX", "optY", "S0", "S1", "optS")   # [batch][m] c128
+UNIT_VN = ("Zb1", "Zb2", "Nb1", "Nb2", "X", "Xcur", "optX")                               # [batch][n] c128
+
+
+class UnitArgs(C.Structure):
+    """Mirror of ``ace_unit_args`` (include/ace.h)."""
+    _fields_ = ([(k, C.c_int32) for k in ("op", "batch", "n", "m", "it", "it_end", "maxiter", "q", "fixed_iters", "guard",
+                                          "done_count", "mspcount", "lazy", "use_la", "use_ax", "yn_copy", "msp", "ctl",
+                                          "np", "msp_fail_it", "waves", "reserved")]
+                + [(k, C.c_double) for k in ("tol_rel", "tol_abs", "rho", "room", "sentinel")]
+                + [("fl", C.c_double * 4)]
+                + [(k, _dp) for k in ("A", "B") + UNIT_VM + UNIT_VN + ("state",)]
+                + [("flags", _ip), ("rank_one", _bp)]
+                + [(k, _dp) for k in ("K_out", "G_out", "c_out", "B_out")]
+                + [(k + "_out", _dp) for k in UNIT_VM + UNIT_VN + ("state",)]
+                + [(k, _ip) for k in ("flags_out", "done_count_out", "mspcount_out", "resume", "steps", "vecw", "ready",
+                                      "guard_ok")])
+
+
 def _load():
     if not LIB_PATH.exists():
         raise ImportError(
@@ -336,6 +355,8 @@ def _load():
     lib.ace_pc_host.restype = C.c_int
     lib.ace_pl_host.argtypes = [C.POINTER(PlArgs)]
     lib.ace_pl_host.restype = C.c_int
+    lib.ace_unit_host.argtypes = [C.POINTER(UnitArgs)]
+    lib.ace_unit_host.restype = C.c_int
     lib.ace_last_error.argtypes = []
     lib.ace_last_error.restype = C.c_char_p
     lib.ace_version.argtypes = []

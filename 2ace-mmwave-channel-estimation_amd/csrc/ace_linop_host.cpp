@@ -6,8 +6,9 @@
 // the caller's mu / vbound / done / nzero / avok (every other field zero), and each operator makes
 // the launcher calls admm_run makes for it on the chosen path (ace_admm.cpp: applyA / applyMM /
 // applyAH, the fused and int8 branches of the iteration).  The fused kernels whose control state
-// is the solver's (gyk / gyf / msr, the FUSE epilogue of i8ah_kernel) are not reachable; pgk and the
-// private code-image setup have an entry of their own (ace_pc_host, ace_pc_host.cpp).
+// is the solver's (gyk / gyf / msr, the FUSE epilogue of i8ah_kernel) have an entry of their own
+// (ace_unit_host, ace_unit_host.cpp), as have pgk and the private code-image setup (ace_pc_host,
+// ace_pc_host.cpp).
 #include "ace_host.hpp"
 
 namespace ace {

@@ -7,9 +7,10 @@
 // the launcher picks the kernel as it does in a solve: zstep1w_kernel at r = 1, zstep_kernel otherwise.
 // The Y-step sums and dual terms are the caller's (yfused = 1, as gyk_kernel leaves them); the four-wave
 // kernel forms its dual terms from Y / K Y buffers, which are zero here.  The producers of the Z-step's
-// inputs that carry solver state -- the fused apply_AH (xfuse), the A2only m-space steady state (msp) and the
-// compact launch -- are not reachable.  The A2nuclear m-space state and its lazy dual residual (nms_kernel) have
-// an entry of their own: ace_nms_host (ace_nms_host.cpp).
+// inputs that carry solver state -- the fused apply_AH (xfuse) and the A2only m-space steady state (msp) -- have an
+// entry of their own, ace_unit_host (ace_unit_host.cpp), which runs them with their fused control; the compact
+// launch is not reachable.  The A2nuclear m-space state and its lazy dual residual (nms_kernel) have theirs:
+// ace_nms_host (ace_nms_host.cpp).
 #include "ace_host.hpp"
 
 namespace ace {

@@ -44,6 +44,8 @@
  *                            the inverse, the tiles, A X0, one iteration launch) on host arrays.
  *  ace_pl_host            <- test entry: one operation of the PhaseLift step kernels (each step of the TFOCS
  *                            iteration, its GEMMs, the Cholesky setup, the final vector) on host arrays.
+ *  ace_unit_host          <- test entry: one launch of the unit path's fused iteration kernels (gyk, gyf, the fused
+ *                            apply_AH, the m-space run, its readiness count, opt_X from m-space) on host arrays.
  *
  * Conventions
  *  - Complex values are complex128, interleaved (re, im) doubles.
@@ -584,6 +586,60 @@ typedef struct ace_pl_args {
     int32_t *act_out, *cnt_out, *ok_out, *iters_out, *status_out, *guard_ok;
 } ace_pl_args;
 int ace_pl_host(const ace_pl_args* args);
+
+/* ---- test entry: one launch of the unit path's fused iteration kernels (csrc/ace_i8gemm.hip) on host arrays -----
+ * The kernels that iterate the A2only r = 1 solve on a shared phase-code A, one launcher call at a time
+ * (tests/test_gpu_unit.py compares them with the references of tests/unit_ref.py).  The entry builds the operators
+ * from A as a solve does (linops_carve / linops_setup with the int8 digit planes), fills GykArgs, ZArgs, DualCtl and
+ * MsrArgs the way admm_iterate_split does at iteration `it` (ping-pong choices by it & 1 and q, yn_id = 2 - q,
+ * Sold = S[(it + 1) & 1], Snew = S[it & 1], Z = (it & 1) ? Zb1 : Zb2 with the other buffer as Z', fixup_now =
+ * (it == maxiter)), one control block per realisation from state / flags (every other field zero), and calls:
+ *   ACE_UNIT_GYK    launch_gyk: T (use_la = 0: the caller's T; 1: apply_A folded in, from Z, N), g = G T, the Y-step
+ *                   (Yo = Y[q] -> Yn = Y[1 - q], M in place, AX when use_ax), opt_Y (yn_copy = 1: yn_id = 0, copied);
+ *                   lazy = 0: K Y' into KY[1 - q] and dAtY, nAtY; lazy = 1: none, pending tests finished first
+ *   ACE_UNIT_GYF    launch_gyf (lazy, apply_A folded in, AX): the same body, the fused apply_AH pass into Z' (or W
+ *                   into X), and with msp = 1 the m-space entry and steps; ctl = 1: fused_control in place
+ *   ACE_UNIT_AHF    launch_i8_apply_AH with the fused epilogue (i8ah_kernel<false, true>), g from memory
+ *   ACE_UNIT_MSR    launch_msr: iterations it .. it_end - 1 in one launch, `waves` 8 or 4 (m = 256 only)
+ *                   -> resume [1], steps [4], mspcount_out, vecw [1]
+ *   ACE_UNIT_READY  launch_msr_ready -> ready [3]
+ *   ACE_UNIT_OPTX   launch_i8_msp_optx: optS (S0 / S1 where optsrc is 4 / 5), Zb1 / Zb2 by z0id -> optX
+ * and hands back the f64 K, G [m][m] c128 and c8 = {c, c^2} the setup produced (K_out, G_out, c_out; may be NULL).
+ * Per-realisation arrays (HOST; c128 as (re, im) doubles): B [b][m] f64; T, g, Y0, Y1, KY0, KY1, M, AX, optY, S0, S1,
+ * optS [b][m] c128; Zb1, Zb2, Nb1, Nb2, X, Xcur, optX [b][n] c128.  One the caller leaves NULL starts from `sentinel`,
+ * and each is followed by `guard` doubles of `sentinel`; each comes back, guard included, in its `_out` array (may be
+ * NULL).  rank_one [b] bytes (may be NULL: the profile np, fl[] for every realisation).  The N of the previous iterate
+ * (Nb1 at odd `it`, else Nb2) is read only for realisations with nzero = 0 and avok = 0; it is not required, so a
+ * caller with such realisations supplies it (a NULL one holds the sentinel like any other buffer).
+ *   state, state_out [batch][ACE_UNIT_NSTATE]: mu, last_res, opt_obj, nB, vbound, obj2, nAX2, nY2, nJM2, dY2, dAtY,
+ *          nAtY, kf0, kf1, kf2, kf3, kfcum, pd_dZ2, pd_nZ2, pd_rc, fs0, fs3   (NULL state: zeros, mu = 1)
+ *   flags, flags_out [batch][ACE_UNIT_NFLAG]: iters, done, status, nzero, avok, optsrc, optysrc, kfok, dpend, fzit,
+ *          zit, mzit, msp, z0id, msp_pad, mres
+ *   done_count / mspcount (and _out): the batch's counts of stopped realisations and of m-space steps before / after
+ *   guard_ok: 1 when the control block after the batch's and every control-block field not listed above are as
+ *          they were
+ * Checked before any HIP call: ACE_ERR_ARG for an unknown op, batch, n or m < 1, a negative guard, it < 1, q not 0 / 1,
+ * rho <= 0, np outside 0..4, it_end <= it or waves not 8 / 4 (MSR) and a NULL required array (named in
+ * ace_last_error()); ACE_ERR_UNSUPPORTED for m > 256, for MSR at m != 256 and for a refused LDS request or a
+ * codebook the int8 setup does not take.  Synchronous; allocates its own device memory. */
+enum { ACE_UNIT_GYK = 0, ACE_UNIT_GYF, ACE_UNIT_AHF, ACE_UNIT_MSR, ACE_UNIT_READY, ACE_UNIT_OPTX, ACE_UNIT_NOPS };
+#define ACE_UNIT_NSTATE 22
+#define ACE_UNIT_NFLAG 16
+typedef struct ace_unit_args {
+    int32_t op, batch, n, m, it, it_end, maxiter, q, fixed_iters, guard, done_count, mspcount;
+    int32_t lazy, use_la, use_ax, yn_copy, msp, ctl, np, msp_fail_it, waves, reserved;
+    double tol_rel, tol_abs, rho, room, sentinel;
+    double fl[4];
+    const double *A, *B, *T, *g, *Y0, *Y1, *KY0, *KY1, *M, *AX, *optY, *S0, *S1, *optS;
+    const double *Zb1, *Zb2, *Nb1, *Nb2, *X, *Xcur, *optX, *state;
+    const int32_t* flags;
+    const unsigned char* rank_one;
+    double *K_out, *G_out, *c_out;
+    double *B_out, *T_out, *g_out, *Y0_out, *Y1_out, *KY0_out, *KY1_out, *M_out, *AX_out, *optY_out, *S0_out, *S1_out;
+    double *optS_out, *Zb1_out, *Zb2_out, *Nb1_out, *Nb2_out, *X_out, *Xcur_out, *optX_out, *state_out;
+    int32_t *flags_out, *done_count_out, *mspcount_out, *resume, *steps, *vecw, *ready, *guard_ok;
+} ace_unit_args;
+int ace_unit_host(const ace_unit_args* args);
 
 /* ---- driver-level boundary (MATLAB Engine calls of main/main.py:308, :427-437) ------------
  *   [H_amp,H_angle] = channel_recovery_ADMM_v2_simulation_<A2only|A2nuclear|multiresolution|phaselift>(

@@ -107,7 +107,8 @@ def test_two_stage_batch_invariance(gpu):
 
 @pytest.mark.parametrize("path", [1, 2])
 def test_smaller_side(gpu, path):
-    """PhaseLift's default (path + 4): with more than half of the eigenvalues above tau the solver returns the
+    """Side mode (path + 4; off by default in ace_phaselift_host.cpp, ACE_PROX_SIDE=1 selects it): with more than
+    half of the eigenvalues above tau the solver returns the
     pairs at or below it, and X = (A - tau I) + sum_{lam <= tau} (tau - lam) v v^H is the same shrunk projector."""
     from ace_amd import prox_eig_host
     rng = np.random.default_rng(31)
