@@ -689,7 +689,7 @@ size_t ao_ws_bytes(int designs, int P, int n, int nrows_max) {
     Carver cv{nullptr};
     AoBufs b;
     ao_carve(cv, designs, P, n, nrows_max, &b);
-    return cv.off;
+    return cv.off + 256;   // (the base is rounded up to 256 B)
 }
 
 }  // namespace
@@ -720,7 +720,7 @@ extern "C" int ace_aopt_select_batch(const ace_aopt_cfg* cfg, int designs, int P
     if (!workspace || workspace_bytes < need)
         return fail(ACE_ERR_WORKSPACE, "aopt: workspace of %zu B, need %zu B", workspace ? workspace_bytes : (size_t)0, need);
     hipStream_t s = (hipStream_t)stream;
-    Carver cv{(char*)workspace};
+    Carver cv{(char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255)};
     AoBufs b;
     ao_carve(cv, designs, P, n, nrows_max, &b);
     const d2* Fc = (const d2*)F;

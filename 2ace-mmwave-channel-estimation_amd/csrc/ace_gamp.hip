@@ -700,7 +700,7 @@ int ga_check_args(const ace_gamp_cfg* cfg, int batch, int d, int N, const double
 
 size_t ga_ws_bytes(int batch, int d, int N) {
     const size_t ng = ((size_t)batch + GA_RB - 1) / GA_RB;
-    return (ng * ga_group_doubles(d, N) * sizeof(double) + 255) & ~(size_t)255;
+    return ((ng * ga_group_doubles(d, N) * sizeof(double) + 255) & ~(size_t)255) + 256;   // (the base is rounded up to 256 B)
 }
 
 }  // namespace
@@ -760,7 +760,7 @@ extern "C" int ace_gamp_solve_batch(const ace_gamp_cfg* cfg, int batch, int d, i
     a.em_iters = em_iters;
     a.trace = trace;
     a.status = status;
-    a.ws = (double*)workspace;
+    a.ws = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     const int nblk = (batch + GA_RB - 1) / GA_RB;
     hipLaunchKernelGGL(gamp_kernel, dim3(nblk), dim3(GA_NT), lds, (hipStream_t)stream, a);
     ACE_HIP(hipGetLastError());

@@ -364,7 +364,7 @@ int om_check_args(int batch, int d, int N, int kmax, double tol, const double* D
 }
 
 size_t om_ws_bytes(int batch, int d, int kmax) {
-    return ((size_t)batch * om_ws_entries(d, kmax) * sizeof(d2) + 255) & ~(size_t)255;
+    return (((size_t)batch * om_ws_entries(d, kmax) * sizeof(d2) + 255) & ~(size_t)255) + 256;   // (the base is rounded up to 256 B)
 }
 
 }  // namespace
@@ -395,7 +395,7 @@ extern "C" int ace_omp_solve_batch(int batch, int d, int N, int kmax, double tol
         return fail(ACE_ERR_UNSUPPORTED, "omp: omp_kernel needs %zu B of dynamic LDS, budget %zu B", lds, lds_dyn_budget(kern));
     const int nblk = (batch + OM_RB - 1) / OM_RB;
     hipLaunchKernelGGL(omp_kernel, dim3(nblk), dim3(OM_NT), lds, (hipStream_t)stream, batch, d, N, kmax, tol, (const d2*)D,
-                       colscale, (const d2*)Y, idx, (d2*)coef, count, resnorm, status, (d2*)x, (d2*)workspace);
+                       colscale, (const d2*)Y, idx, (d2*)coef, count, resnorm, status, (d2*)x, (d2*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255));
     ACE_HIP(hipGetLastError());
     return ACE_OK;
 }

@@ -969,7 +969,7 @@ int pg_check_args(const ace_prgamp_cfg* cfg, int batch, int m, int N, const doub
 
 size_t pg_ws_bytes(int batch, int m, int N) {
     const size_t ng = ((size_t)batch + PG_RB - 1) / PG_RB;
-    return (ng * pg_group_doubles(m, N) * sizeof(double) + 255) & ~(size_t)255;
+    return ((ng * pg_group_doubles(m, N) * sizeof(double) + 255) & ~(size_t)255) + 256;   // (the base is rounded up to 256 B)
 }
 
 }  // namespace
@@ -1033,7 +1033,7 @@ extern "C" int ace_prgamp_solve_batch(const ace_prgamp_cfg* cfg, int batch, int 
     a.status = status;
     a.trace = trace;
     a.vals = vals;
-    a.ws = (double*)workspace;
+    a.ws = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     // the slots of calls that never run read 0
     const size_t nslot = (size_t)batch * cfg->max_try * ((size_t)cfg->nit_em + 1);
     if (trace) ACE_HIP(hipMemsetAsync(trace, 0, nslot * 2 * sizeof(int32_t), (hipStream_t)stream));

@@ -425,7 +425,7 @@ size_t sc_ws_bytes(const ace_scenario_cfg* cfg, int count, int m, int n, int Mr)
     Carver cv{nullptr};
     ScBufs b;
     sc_carve(cv, count, m, n, cfg->noise_model == 1 ? Mr : 0, &b);
-    return cv.off;
+    return cv.off + 256;   // (the base is rounded up to 256 B)
 }
 
 }  // namespace
@@ -468,7 +468,7 @@ extern "C" int ace_synth_scenario(const ace_scenario_cfg* cfg, uint64_t seed, in
     if (!workspace || workspace_bytes < need)
         return fail(ACE_ERR_WORKSPACE, "scenario: workspace of %zu B, need %zu B", workspace ? workspace_bytes : (size_t)0, need);
     hipStream_t s = (hipStream_t)stream;
-    Carver cv{(char*)workspace};
+    Carver cv{(char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255)};
     ScBufs b;
     sc_carve(cv, count, m, n, mr, &b);
 

@@ -55,7 +55,10 @@
  *    X0/X[batch][n] (c128), Y[batch][m] (c128).
  *  - All pointers passed to ace_admm_solve_batch / ace_synth_* are DEVICE
  *    pointers; the caller owns every buffer (no allocation crosses the ABI).
- *    The workspace must be ace_admm_workspace_size() bytes, 256-B aligned.
+ *  - Workspaces (every `workspace` / `workspace_bytes` pair): DEVICE memory of at least the matching
+ *    *_workspace_size() bytes.  It may start at any address: every entry rounds the base up to 256 B before it
+ *    carves, and every size query already includes that slack.  An entry reads nothing from its workspace that it has
+ *    not written in the same call, so the contents on entry do not matter (tests/test_gpu_arena.py).
  *  - `stream` is a hipStream_t (NULL = default stream).  Calls are
  *    asynchronous on that stream except where noted; they are re-entrant per
  *    stream (no global mutable state besides the thread-local error text).

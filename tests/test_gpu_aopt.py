@@ -117,11 +117,9 @@ def test_duplicated_candidates_go_to_the_smaller_index(gpu, shape):
     assert 3 in res.rowlist[0] and 40 not in res.rowlist[0]
 
 
-def test_batch_invariance(gpu):
-    """Designs with ragged row counts on one F, twice over two tile groups (ten designs), equal their single-design
-    calls bit for bit, with and without Minv_out, and the restatement."""
-    import torch
-    from ace_amd import design
+def ragged_designs():
+    """Ten designs with ragged row counts on one F, twice over two tile groups: (F, nrows [10], init [10][80], the five
+    row counts, their start rows)."""
     F, _ = make(64, 200, 80, 5)
     rng = np.random.default_rng(77)
     Ms = [8, 24, 40, 16, 80]
@@ -131,6 +129,15 @@ def test_batch_invariance(gpu):
     init = np.full((10, 80), 199, np.int32)            # the padding is never read as a start row
     for d, i in enumerate(order):
         init[d, :Ms[i]] = inits[i]
+    return F, nrows, init, Ms, inits
+
+
+def test_batch_invariance(gpu):
+    """Designs with ragged row counts on one F, twice over two tile groups (ten designs), equal their single-design
+    calls bit for bit, with and without Minv_out, and the restatement."""
+    import torch
+    from ace_amd import design
+    F, nrows, init, Ms, inits = ragged_designs()
     Fd = torch.as_tensor(F, device=gpu)
     call = lambda nr, ini, mv: design.aopt_select_batch(Fd, torch.as_tensor(nr, device=gpu),   # noqa: E731
                                                         torch.as_tensor(ini, device=gpu), want_minv=mv)
