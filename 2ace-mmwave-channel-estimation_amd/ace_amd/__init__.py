@@ -35,5 +35,9 @@ from . import design  # noqa: F401
 from .scenario import scenario_batch, ScenarioResult  # noqa: F401
 from ._lib import ScenarioCfg, scenario_cfg  # noqa: F401
 from . import scenario  # noqa: F401
+from .recovery_eval import (evaluate_recovery_host, evaluate_recovery_batch, recovery_tables, sweep_tables,  # noqa: F401
+                            RecoveryEval, RecoveryTables, SweepTables, METRICS_RECOVERY)
+from ._lib import ACE_ST_RECEVAL_NOSWEEP  # noqa: F401
+from . import recovery_eval  # noqa: F401
 
 __version__ = LIB.ace_version().decode()

@@ -35,6 +35,7 @@ ACE_ST_GAMP_FAILED = 8192
 ACE_ST_PRGAMP_FAILED = 16384
 ACE_ST_PRGAMP_MAXTRY = 32768
 ACE_ST_AOPT_SINGULAR = 65536
+ACE_ST_RECEVAL_NOSWEEP = 131072
 
 ACE_TRAIN_SHARED = 0
 ACE_TRAIN_PER_REALISATION = 1
@@ -277,6 +278,18 @@ def _load():
     lib.ace_evaluate_batch.restype = C.c_int
     lib.ace_evaluate_host.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, up]
     lib.ace_evaluate_host.restype = C.c_int
+    rv_head = [C.c_int] * 6
+    rv_mid = [C.c_int, C.c_int, C.c_double, C.c_double]
+    lib.ace_evaluate_recovery_batch.argtypes = (rv_head + [vp] * 4 + rv_mid + [vp] * 6 + [C.c_int, C.c_int] + [vp] * 4
+                                                + [vp, vp, vp, vp])
+    lib.ace_evaluate_recovery_batch.restype = C.c_int
+    lib.ace_evaluate_recovery_host.argtypes = (rv_head + [dp] * 4 + rv_mid + [dp] * 4 + [ip, ip] + [C.c_int, C.c_int]
+                                               + [dp] * 4 + [dp, dp, up])
+    lib.ace_evaluate_recovery_host.restype = C.c_int
+    lib.ace_beam_peak_angles.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp, vp]
+    lib.ace_beam_peak_angles.restype = C.c_int
+    lib.ace_beam_peak_angles_host.argtypes = [C.c_int, C.c_int, C.c_double, dp, dp]
+    lib.ace_beam_peak_angles_host.restype = C.c_int
     lib.ace_rss_evaluate_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.ace_rss_evaluate_batch.restype = C.c_int
     lib.ace_rss_evaluate_host.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, dp, dp, up]

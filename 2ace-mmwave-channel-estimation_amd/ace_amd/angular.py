@@ -76,6 +76,45 @@ def sweep_beams(n_ant, M, search_deg=SEARCH_DEG):
     return quantize_ps(steering(n_ant, np.sin(np.deg2rad(centres))) * np.sqrt(n_ant)), centres
 
 
+def directional_beams(n_ant, M, search_deg=SEARCH_DEG):
+    """Directional_Beam_Angular.m:72-85 for one side: (beams [M][n_ant], centre angles in degrees [M]).  An alias of
+    ``sweep_beams``: the reference builds pattern 1's probes (Directional_Beam_Angular.m:79-85, steering vectors over
+    sqrt(N)) and pattern 2's sweep beams (MyBeamSweeping.m:101-108, unnormalised) at the same partition centres, and
+    Quantize_PS keeps only the phases, so the two give the same F and W.  Unit modulus here; the reference's beams are
+    these over sqrt(n_ant) (Quantize_PS.m:70)."""
+    return sweep_beams(n_ant, M, search_deg)
+
+
+def peak_angle_grid():
+    """The 36001 angles -90 : 0.005 : 90 of MyBeamSweeping.m:134, built from both ends as MATLAB's colon does."""
+    i = np.arange(36001)
+    return np.where(i <= 18000, -90.0 + 0.005 * i, 90.0 - 0.005 * (36000 - i))
+
+
+def beam_peak_angles(beams):
+    """Pattern 1's angle estimate (MyBeamSweeping.m:134-154) on the GPU (``ace_beam_peak_angles``): for each beam
+    [M][n_ant] the first angle of ``peak_angle_grid()`` that maximises |f^H a(theta)|, a the unnormalised steering
+    vector; degrees [M].  Once per sweep point.  A numpy array in gives a numpy array; a device tensor a device tensor."""
+    import ctypes as C
+    from ._lib import LIB, check
+    if isinstance(beams, np.ndarray) or not hasattr(beams, "is_cuda"):
+        b = np.ascontiguousarray(np.atleast_2d(np.asarray(beams, np.complex128)))
+        if b.ndim != 2 or not 1 <= b.shape[1] <= 32 or b.shape[0] < 1:
+            raise ValueError(f"beams must be [M][n_ant] with 1 <= n_ant <= 32, got {b.shape}")
+        out = np.empty(b.shape[0], np.float64)
+        dp = lambda a: a.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        check(LIB.ace_beam_peak_angles_host(b.shape[0], b.shape[1], float(KAPPA), dp(b), dp(out)))
+        return out
+    import torch
+    if not beams.is_cuda or beams.dtype != torch.complex128 or beams.dim() != 2 or not 1 <= beams.shape[1] <= 32:
+        raise ValueError("beams must be a complex128 device tensor [M][n_ant] with 1 <= n_ant <= 32")
+    b = beams.contiguous()
+    out = torch.empty(b.shape[0], dtype=torch.float64, device=b.device)
+    check(LIB.ace_beam_peak_angles(int(b.shape[0]), int(b.shape[1]), float(KAPPA), b.data_ptr(), out.data_ptr(),
+                                   torch.cuda.current_stream(b.device).cuda_stream))
+    return out
+
+
 def kron_codebook(Ft, Wr):
     """The measurement matrix kron(F.', W') of Generate_Sensing_Matrix.m for precoders Ft [Mt][tx] and combiners Wr
     [Mr][rx] given as rows: A [Mt*Mr][tx*rx] with A[it Mr + q][t rx + r] = Ft[it][t] conj(Wr[q][r]), the synth's vec(H)

@@ -16,7 +16,10 @@ the rows asked for: a realisation's metrics are a function of (seed, M, i, chunk
 reproduces its rows of the full run bit for bit.
 
 ``vs_snr`` is the sweep over SNR of ``Vs_SNR.m`` in the reference's own scenario (``scenario.scenario_batch``), on the
-same chunk grid.
+same chunk grid.  ``vs_sr`` is ``VS_SR_par.m``: the mean angle estimation error against the number of measurements per
+searching area.  The sparse recoveries can be scored with the reference's own ``Evaluation_Recovery``
+(``recovery_eval.evaluate_recovery_batch``, 15 columns): ``vs_sr`` always does, ``vs_m_sparse`` and ``vs_snr`` with
+``columns="recovery"``.
 """
 from __future__ import annotations
 
@@ -132,13 +135,48 @@ def vs_m_minl2(tx, rx, M_list, count, *, snr_db=30.0, L=3, seed, first=0, maxite
             "columns": METRICS, "r_used": r_used, "quality": quality, "stage_iters": stage_iters}
 
 
+SWEEP1_SEED = 0x9E3779B9   # added to the seed for sweep pattern 1's noise: patterns 1 and 2 draw independently
+
+
+def _dense_z(r):
+    """The sparse vector of a recovery [batch][N] on the device: a GAMP result's ``xhat``, an OMP result's support and
+    coefficients scattered into zeros (coef is 0 past count)."""
+    import torch
+    if hasattr(r, "xhat"):
+        return r.xhat.contiguous()
+    if r.x is not None:
+        return r.x.contiguous()
+    z = torch.zeros((r.idx.shape[0], r.N, 2), dtype=torch.float64, device=r.idx.device)
+    z.scatter_add_(1, r.idx.clamp(min=0).long()[:, :, None].expand(-1, -1, 2), torch.view_as_real(r.coef))
+    return torch.view_as_complex(z)
+
+
+def _sweep_picks(Hraw, tx, rx, Mt, Mr, snr_db, seed, first, search_deg):
+    """[batch][2][2] int32 on the device: (ind_F, ind_W) zero-based of the reference's sweep pattern 1 and pattern 2
+    (Evaluation_Recovery.m:232-233).  The two run the same quantised beams (``angular.directional_beams``) on
+    independent noise draws: pattern 2 ``angular.beam_sweep``'s at ``seed``, pattern 1 at ``seed + SWEEP1_SEED``."""
+    import torch
+    from . import angular
+    pk = []
+    for sd in (seed + SWEEP1_SEED, seed):
+        _, _, p, q = angular.beam_sweep(Hraw, tx, rx, Mt, Mr, snr_db=snr_db, seed=sd, first=first, search_deg=search_deg)
+        pk.append(torch.stack([p, q], dim=1))
+    return torch.stack(pk, dim=1).to(torch.int32).contiguous()
+
+
+def _check_columns(columns):
+    if columns not in ("h", "recovery"):
+        raise ValueError(f"columns must be 'h' or 'recovery', got {columns!r}")
+    return columns == "recovery"
+
+
 SPARSE = ("plomp", "plomp_2s", "perfect_cs")
 SPARSE_GAMP = ("plgamp", "perfect_cs_gamp")
 SPARSE_PRGAMP = ("prgamp",)
 
 
 def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=0, pl_maxits=4000, tol=1e-12,
-                device=None, chunk=CHUNK, gamp=False, prgamp=False, max_try=100) -> dict:
+                device=None, chunk=CHUNK, gamp=False, prgamp=False, max_try=100, columns="h") -> dict:
     """The sparse recoveries of ``sparse.py`` on ``vs_m``'s sweep: the same chunk grid, codebook, channels and noise
     draws (``synth_problem`` at (seed, M, realisation index)), so the curves stand next to ``vs_m``'s.  Per M and
     realisation, the four ``evaluate_batch`` columns ([nM][count][4] each, keys ``SPARSE``) of
@@ -178,6 +216,13 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     ``gain_percsi_ana`` [nM][count] (``evaluate_batch(H, H)``: the H scored is ``vs_m``'s) and the means.  Only
     metrics, counts and status words leave the device.
 
+    ``columns="recovery"`` adds the reference's own score of these methods, ``Evaluation_Recovery``
+    (``recovery_eval.evaluate_recovery_batch``): per method ``recovery_<key>`` [nM][count][15] (columns
+    ``columns_recovery`` = ``recovery_eval.METRICS_RECOVERY``) and ``status_recovery_<key>``, against the channel at the
+    synth's own scale (the scale of the measurements the recoveries see; MSE_H is not scale-free), the synth's true
+    angles and, for the sweep columns, ``angular.beam_sweep`` with round(sqrt(M)) beams per side run twice on independent
+    noise (patterns 1 and 2).  Every other key and value is bit-identical to the default ``columns="h"``.
+
     Cost.  The two-stage setup runs one host SVD of Phi (M x Qt Qr) per sweep point.  PhaseLift dominates: one
     TFOCS iteration per realisation is an eigendecomposition of an mCS x mCS matrix and two products with P, and
     the reference's ``pl_maxits`` = 4000 at mCS around 150 makes a sweep point of 64 realisations take minutes, a
@@ -188,6 +233,7 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     from .solver import synth_problem
     if tx != rx:
         raise ValueError(f"vs_m_sparse needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
+    want_rec = _check_columns(columns)
     count, first, chunk = int(count), int(first), int(chunk)
     if count < 1 or first < 0 or chunk < 1:
         raise ValueError("count and chunk must be >= 1 and first >= 0")
@@ -212,8 +258,17 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
     percsi = np.empty((len(Ms), count), np.float64)
     mcs = np.empty(len(Ms), np.int64)
     end = first + count
+    rec, rec_st = {}, {}
+    if want_rec:
+        from . import angular, recovery_eval
+        rec = {k: np.full((len(Ms), count, recovery_eval.NCOL), np.nan) for k in out}
+        rec_st = {k: np.zeros((len(Ms), count), np.uint32) for k in out}
+        tb = recovery_eval.recovery_tables(tx, rx)
     for k, M in enumerate(Ms):
         setup, Phi, Ah = None, None, synth.codebook(seed, M, n)
+        if want_rec:
+            nb_sw = max(1, int(round(math.sqrt(M))))
+            sw = recovery_eval.sweep_tables(tx, rx, nb_sw, nb_sw)
         for c0 in range(first // chunk * chunk, end, chunk):
             A, B, _, H = synth_problem(seed, c0, chunk, M, tx, rx, L=L, snr_db=snr_db, device=dev)
             if setup is None:
@@ -243,11 +298,23 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
             lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
             rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
             percsi[k, rows] = evaluate_batch(H, H, tx, rx).gain_ana[sel].cpu().numpy()
+            res_aux = {}
             for name, r in res.items():
                 ev = evaluate_batch(r.channel(AD), H, tx, rx)
                 out[name][k, rows] = ev.metrics[sel].cpu().numpy()
                 # the evaluator's bits and the OMP stage's (ACE_ST_EVAL_DEGENERATE there: a non-finite PhaseLift output)
                 stat[name][k, rows] = (ev.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
+                if want_rec:
+                    if "Hraw" not in res_aux:
+                        tru = [synth.paths(seed, c0 + b, L) for b in range(chunk)]
+                        res_aux["Hraw"] = up(Hh)
+                        res_aux["aod"], res_aux["aoa"] = up(np.stack([t[0] for t in tru])), up(np.stack([t[1] for t in tru]))
+                        res_aux["picks"] = _sweep_picks(res_aux["Hraw"], tx, rx, nb_sw, nb_sw, snr_db, seed, c0,
+                                                        angular.SEARCH_DEG)
+                    rv = recovery_eval.evaluate_recovery_batch(_dense_z(r), res_aux["Hraw"], res_aux["aod"], res_aux["aoa"],
+                                                               tb, noise_power=noise_power, picks=res_aux["picks"], sweep=sw)
+                    rec[name][k, rows] = rv.metrics[sel].cpu().numpy()
+                    rec_st[name][k, rows] = (rv.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
                 if name in tries:
                     tries[name][k, rows] = r.counts[sel, 0].cpu().numpy()
                 elif name in emi:
@@ -256,7 +323,17 @@ def vs_m_sparse(tx, rx, M_list, count, *, s=None, snr_db=30.0, L=3, seed, first=
                     cnt[name][k, rows] = r.count[sel].cpu().numpy()
     return {"M": np.asarray(Ms, np.int64), "mCS": mcs, "s": s, **out, "columns": METRICS, "gain_percsi_ana": percsi,
             **{f"status_{k}": v for k, v in stat.items()}, **{f"count_{k}": v for k, v in cnt.items()},
-            **{f"em_iters_{k}": v for k, v in emi.items()}, **{f"tries_{k}": v for k, v in tries.items()}, "mean": {k: v.mean(axis=1) for k, v in out.items()}}
+            **{f"em_iters_{k}": v for k, v in emi.items()}, **{f"tries_{k}": v for k, v in tries.items()}, "mean": {k: v.mean(axis=1) for k, v in out.items()},
+            **_recovery_keys(rec, rec_st)}
+
+
+def _recovery_keys(rec, rec_st):
+    """The keys ``columns="recovery"`` adds to a sweep's dict (none for the default)."""
+    if not rec:
+        return {}
+    from .recovery_eval import METRICS_RECOVERY
+    return {**{f"recovery_{k}": v for k, v in rec.items()}, **{f"status_recovery_{k}": v for k, v in rec_st.items()},
+            "columns_recovery": METRICS_RECOVERY, "mean_recovery": {k: v.mean(axis=1) for k, v in rec.items()}}
 
 
 BASELINES = ("gain_percsi_ana", "gain_percsi_dig", "aoda_err_est", "gain_est_aoda", "gain_sweep", "aoda_err_sweep")
@@ -357,7 +434,7 @@ VS_SNR_SPARSE = ("plomp", "plgamp", "perfect_cs", "noisy_cs")
 
 def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", "perfect_cs", "noisy_cs"), L=1,
            rician_k=5, search_deg=40.0, on_grid=False, noise="combiner", seed, first=0, chunk=CHUNK, pl_maxits=4000,
-           maxiter=None, device=None) -> dict:
+           maxiter=None, device=None, columns="h") -> dict:
     """The reference's ``Vs_SNR`` loop (Numerical_Simulation/main_programs/Vs_SNR.m:100-108: one dominant path with
     ``rician_k`` NLOS paths at the 7 dB K-factor, a searching area of ``search_deg`` degrees, M x M directional beams)
     with every step on the GPU: per SNR and realisation the scenario generator (``scenario.scenario_batch``), the
@@ -382,7 +459,13 @@ def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", 
 
     Returns ``snr`` [nSNR], per method its four ``evaluate_batch`` columns [nSNR][count][4] (key = the method's name),
     ``status_<method>`` [nSNR][count], ``mean`` (per method [nSNR][4]), ``gain_percsi_ana`` [nSNR][count]
-    (``evaluate_batch(H, H)`` on the channel at the reference's scale), ``mCS`` and ``columns``."""
+    (``evaluate_batch(H, H)`` on the channel at the reference's scale), ``mCS`` and ``columns``.
+
+    ``columns="recovery"`` adds, for the sparse methods, the score Vs_SNR.m:192-194 gives them, ``Evaluation_Recovery``
+    (``recovery_eval.evaluate_recovery_batch``): ``recovery_<method>`` [nSNR][count][15] (columns ``columns_recovery``),
+    ``status_recovery_<method>`` and ``mean_recovery``, with the scenario's true angles and the two sweep patterns on
+    the M x M directional beams (``angular.beam_sweep`` on independent noise draws).  Every other key and value is
+    bit-identical to the default ``columns="h"``."""
     import torch
     from . import angular, sparse
     from .engine import randperm
@@ -398,6 +481,7 @@ def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", 
         raise ValueError(f"vs_snr needs tx == rx (got {tx} x {rx}): the synth's vec(H) order has rx leading")
     if noise not in ("combiner", "iid"):
         raise ValueError(f"noise must be 'combiner' or 'iid', got {noise!r}")
+    want_rec = _check_columns(columns)
     count, first, chunk, M = int(count), int(first), int(chunk), int(M)
     if count < 1 or first < 0 or chunk < 1 or M < 1:
         raise ValueError("count, chunk and M must be >= 1 and first >= 0")
@@ -423,6 +507,13 @@ def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", 
         Phi = (As @ AD).contiguous()
         setup = sparse.two_stage_setup(Phi.cpu().numpy(), s).to(dev)
         mcs = setup.mCS
+    rec, rec_st = {}, {}
+    if want_rec and sp:
+        from . import recovery_eval
+        rec = {k: np.empty((len(snrs), count, recovery_eval.NCOL), np.float64) for k in sp}
+        rec_st = {k: np.zeros((len(snrs), count), np.uint32) for k in sp}
+        tb = recovery_eval.recovery_tables(tx, rx, None, None, search_deg)
+        sw = recovery_eval.sweep_tables(tx, rx, M, M, search_deg)
     if ad:
         Ar = torch.empty((1, m, n), dtype=torch.complex128, device=dev)
         check(LIB.ace_synth_codebook(seed, -1, 1, m, n, Ar.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
@@ -436,7 +527,7 @@ def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", 
             if sp:
                 cfg = scenario_cfg(snr_db=snr, noise_model=1 if noise == "combiner" else 0, **base)
                 sc = scenario_batch(seed, c0, chunk, tx, rx, As, cfg, Wd if noise == "combiner" else None,
-                                    want=("vecH", "y", "y_noisy", "B_raw"))
+                                    want=("vecH", "y", "y_noisy", "B_raw") + (("paths",) if rec else ()))
                 H = sc.vecH
                 if "plomp" in sp or "plgamp" in sp:
                     ts, sig = sparse.plomp_stage1(Phi, sc.B_raw * sc.B_raw, s, setup=setup, maxIts=int(pl_maxits))
@@ -465,6 +556,147 @@ def vs_snr(tx, rx, M, snr_list, count, *, methods=("A2only", "plomp", "plgamp", 
                 st = ev.status if name in ad else (ev.status | r.status)
                 out[name][k, rows] = ev.metrics[sel].cpu().numpy()
                 stat[name][k, rows] = st[sel].cpu().numpy().view(np.uint32)
+            if rec:
+                aod, aoa = recovery_eval.split_paths(sc.paths, int(L))
+                aod, aoa = aod.contiguous(), aoa.contiguous()
+                picks = _sweep_picks(sc.vecH, tx, rx, M, M, snr, seed, c0, search_deg)
+                for name in sp:
+                    r = res[name][0]
+                    rv = recovery_eval.evaluate_recovery_batch(_dense_z(r), sc.vecH, aod, aoa, tb,
+                                                               noise_power=sc.noise_power, picks=picks, sweep=sw)
+                    rec[name][k, rows] = rv.metrics[sel].cpu().numpy()
+                    rec_st[name][k, rows] = (rv.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
     return {"snr": np.asarray(snrs, np.float64), "M": M, "mCS": mcs, "s": s, **out, "columns": METRICS,
             "gain_percsi_ana": percsi, **{f"status_{k}": v for k, v in stat.items()},
-            "mean": {k: v.mean(axis=1) for k, v in out.items()}}
+            "mean": {k: v.mean(axis=1) for k, v in out.items()}, **_recovery_keys(rec, rec_st)}
+
+
+# the table of VS_SR_par.m:74-99: searching area -> (M, G) pairs
+VS_SR_AREAS = (20, 30, 40, 50, 60, 70, 80)
+VS_SR_M = ((2, 3, 4, 5), (4, 5, 6, 7), (5, 6, 7, 8, 9), (6, 7, 8, 9, 10, 11), (8, 9, 10, 11, 12), (9, 10, 11, 12, 13),
+           (10, 11, 12, 13, 14))
+VS_SR_G = ((25, 35, 45, 55), (25, 40, 55, 60), (25, 40, 55, 60, 70), (25, 40, 45, 55, 65, 70), (40, 50, 55, 60, 70),
+           (40, 55, 60, 70, 75), (45, 55, 60, 70, 75))
+VS_SR_MAEE = (0.6, 0.8, 1.0)   # VS_SR_par.m:105
+VS_SR_ANTENNAS = 12            # sub_VS_SR_par.m:56-57
+
+
+def vs_sr(tx=VS_SR_ANTENNAS, rx=VS_SR_ANTENNAS, area_list=VS_SR_AREAS, M_lists=VS_SR_M, G_lists=VS_SR_G, count=100, *,
+          methods=("plomp", "plgamp", "perfect_cs", "noisy_cs"), snr_db=0.0, rician_k=5, seed, first=0, chunk=CHUNK,
+          noise="combiner", pl_maxits=4000, maee_set=VS_SR_MAEE, return_inputs=False, device=None) -> dict:
+    """The reference's ``VS_SR_par.m`` / ``sub_VS_SR_par.m``: how side information (a narrower searching area) reduces
+    the training overhead.  Per searching area ``area_list[a]`` (degrees) and per pair ``(M_lists[a][i], G_lists[a][i])``:
+    one dominant path (L = 1) at off-grid angles inside the area with ``rician_k`` NLOS paths
+    (``scenario.scenario_batch``), M x M ``angular.directional_beams`` probes over the area (Directional_Beam_Angular),
+    the dictionary on a grid of NQ = G points per side cut to the area, the two-stage recoveries (``plomp``, ``plgamp``)
+    and the conventional-CS benchmarks (``perfect_cs``, ``noisy_cs``) of ``vs_snr``, and the reference's own score,
+    ``Evaluation_Recovery`` (``recovery_eval.evaluate_recovery_batch``), with the two sweep patterns on the same beams.
+    Every step runs on the GPU; only metrics and status words leave the device.  The defaults are the reference's:
+    12 x 12 antennas (sub_VS_SR_par.m:56-57), SNR 0 dB, the table of VS_SR_par.m:74-99.
+
+    Random numbers are ``vs_snr``'s: realisation b of the call is realisation ``first + b`` of the sweep, its draws
+    depend on (seed, first + b) alone (common random numbers across the sweep points, where the reference draws afresh),
+    and chunks lie on the grid of the realisation index, so shards compose.
+
+    Returns ``area`` [nArea], ``M`` and ``G`` [nArea][nM] (nM the longest list; -1 pads the shorter ones), ``nM``
+    [nArea], per method its 15 columns [nArea][nM][count][15] (key = the method's name, columns ``columns`` =
+    ``recovery_eval.METRICS_RECOVERY``, NaN in the padding), ``status_<method>`` [nArea][nM][count] (the evaluator's bits
+    or-ed with the solver's), ``mean`` (per method [nArea][nM][15]), ``mCS`` [nArea][nM], and the read-out of
+    VS_SR_par.m:105-125: ``M_at_maee`` (per method [nArea][len(maee_set)]), the M at which the method's mean AoDA_Err
+    (column 1, the MAEE) comes nearest to each value of ``maee_set``, the first on a tie; the reference plots its square.
+    ``return_inputs=True`` also copies each point's channels, paths, picks and recovered vectors to the host
+    (``inputs[a][i]``: a dict), for tests and diagnosis."""
+    import torch
+    from . import angular, recovery_eval, sparse
+    from .scenario import scenario_batch
+    from ._lib import scenario_cfg
+    methods = tuple(methods)
+    bad = [k for k in methods if k not in VS_SNR_SPARSE]
+    if bad or not methods:
+        raise ValueError(f"methods must come from {VS_SNR_SPARSE}, got {bad or methods}")
+    if tx != rx:
+        raise ValueError(f"vs_sr needs tx == rx (got {tx} x {rx}): the sparse recoveries it shares with vs_snr are square-only")
+    if noise not in ("combiner", "iid"):
+        raise ValueError(f"noise must be 'combiner' or 'iid', got {noise!r}")
+    areas = [float(a) for a in area_list]
+    Ml, Gl = [[int(v) for v in r] for r in M_lists], [[int(v) for v in r] for r in G_lists]
+    if len(Ml) != len(areas) or len(Gl) != len(areas) or any(len(a) != len(b) or not a for a, b in zip(Ml, Gl)):
+        raise ValueError("M_lists and G_lists need one list per searching area, of equal non-zero lengths")
+    count, first, chunk = int(count), int(first), int(chunk)
+    if count < 1 or first < 0 or chunk < 1:
+        raise ValueError("count and chunk must be >= 1 and first >= 0")
+    if any(M < 1 or M * M > sparse.D_MAX for r in Ml for M in r):
+        raise ValueError(f"vs_sr: M^2 measurements must be 1..{sparse.D_MAX}, the OMP kernel's row limit")
+    if any(G < 1 for r in Gl for G in r):
+        raise ValueError("vs_sr: the grid sizes must be >= 1")
+    dev = torch.device("cuda" if device is None else device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    nA, nM, NC = len(areas), max(len(r) for r in Ml), recovery_eval.NCOL
+    out = {k: np.full((nA, nM, count, NC), np.nan) for k in methods}
+    stat = {k: np.zeros((nA, nM, count), np.uint32) for k in methods}
+    Mpad, Gpad, mcs = np.full((nA, nM), -1, np.int64), np.full((nA, nM), -1, np.int64), np.full((nA, nM), -1, np.int64)
+    inputs = [[None] * len(r) for r in Ml]
+    end, s = first + count, 1
+    for a, area in enumerate(areas):
+        for i, (M, G) in enumerate(zip(Ml[a], Gl[a])):
+            Mpad[a, i], Gpad[a, i] = M, G
+            Ft, Wr = angular.directional_beams(tx, M, area)[0] / np.sqrt(tx), angular.directional_beams(rx, M, area)[0] / np.sqrt(rx)
+            As, Wd = up(angular.kron_codebook(Ft, Wr)), up(Wr)
+            Phi = (As @ up(sparse.dictionary_2d(tx, rx, G, G, search_deg=area)[0])).contiguous()
+            tb = recovery_eval.recovery_tables(tx, rx, G, G, area)
+            sw = recovery_eval.sweep_tables(tx, rx, M, M, area)
+            setup = None
+            if "plomp" in methods or "plgamp" in methods:
+                setup = sparse.two_stage_setup(Phi.cpu().numpy(), s).to(dev)
+                mcs[a, i] = setup.mCS
+            cfg = scenario_cfg(L=1, rician_k=int(rician_k), search_deg=area, on_grid=0, NQt=G, NQr=G, snr_db=float(snr_db),
+                               noise_model=1 if noise == "combiner" else 0)
+            keep = {} if not return_inputs else {"vecH": [], "paths": [], "picks": [], **{f"z_{k}": [] for k in methods}}
+            for c0 in range(first // chunk * chunk, end, chunk):
+                lo, hi = max(first, c0), min(end, c0 + chunk)   # the rows of this chunk the call asked for
+                rows, sel = slice(lo - first, hi - first), slice(lo - c0, hi - c0)
+                sc = scenario_batch(seed, c0, chunk, tx, rx, As, cfg, Wd if noise == "combiner" else None,
+                                    want=("vecH", "y", "y_noisy", "B_raw", "paths"))
+                res = {}
+                if setup is not None:
+                    ts, sig = sparse.plomp_stage1(Phi, sc.B_raw * sc.B_raw, s, setup=setup, maxIts=int(pl_maxits))
+                    if "plomp" in methods:
+                        res["plomp"] = sparse.omp_batch(ts.C, sig, ts.mCS, 1e-12)
+                    if "plgamp" in methods:
+                        res["plgamp"] = sparse._gamp_stage2(ts, sig, s, sc.noise_power, Phi.shape[1])
+                if "perfect_cs" in methods:
+                    res["perfect_cs"] = sparse.perfect_phase_cs(Phi, sc.y, s)
+                if "noisy_cs" in methods:
+                    res["noisy_cs"] = sparse.noisy_phase_cs(Phi, sc.y_noisy, s)
+                aod, aoa = recovery_eval.split_paths(sc.paths, 1)
+                aod, aoa = aod.contiguous(), aoa.contiguous()
+                picks = _sweep_picks(sc.vecH, tx, rx, M, M, float(snr_db), seed, c0, area)
+                if return_inputs:
+                    keep["vecH"].append(sc.vecH[sel].cpu().numpy())
+                    keep["paths"].append(sc.paths[sel].cpu().numpy())
+                    keep["picks"].append(picks[sel].cpu().numpy())
+                for name, r in res.items():
+                    z = _dense_z(r)
+                    rv = recovery_eval.evaluate_recovery_batch(z, sc.vecH, aod, aoa, tb, noise_power=sc.noise_power,
+                                                               picks=picks, sweep=sw)
+                    out[name][a, i, rows] = rv.metrics[sel].cpu().numpy()
+                    stat[name][a, i, rows] = (rv.status[sel] | r.status[sel]).cpu().numpy().view(np.uint32)
+                    if return_inputs:
+                        keep[f"z_{name}"].append(z[sel].cpu().numpy())
+            if return_inputs:
+                inputs[a][i] = {**{k: np.concatenate(v) for k, v in keep.items()}, "noise_power": sc.noise_power,
+                                "tables": tb, "sweep": sw}
+    mean = {k: v.mean(axis=2) for k, v in out.items()}
+    at = {}
+    for k in methods:
+        at[k] = np.full((nA, len(maee_set)), -1, np.int64)
+        for a in range(nA):
+            maee = mean[k][a, :len(Ml[a]), 1]
+            for j, target in enumerate(maee_set):
+                at[k][a, j] = Ml[a][int(np.argmin(np.abs(maee - float(target))))]   # (:115-118: min takes the first)
+    ret = {"area": np.asarray(areas, np.float64), "M": Mpad, "G": Gpad, "nM": np.asarray([len(r) for r in Ml], np.int64),
+           **out, "columns": recovery_eval.METRICS_RECOVERY, **{f"status_{k}": v for k, v in stat.items()}, "mean": mean,
+           "mCS": mcs, "M_at_maee": at, "maee_set": tuple(float(v) for v in maee_set)}
+    if return_inputs:
+        ret["inputs"] = inputs
+    return ret

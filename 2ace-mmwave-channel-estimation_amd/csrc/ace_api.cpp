@@ -106,6 +106,8 @@ int ace_lds_request(const char* kernel, int m, size_t* bytes) {
     else if (k == "hb2st") *bytes = heev2_request_bytes(m, 1);
     else if (k == "bt2") *bytes = heev2_request_bytes(m, 2);
     else if (k == "scan") *bytes = scan_request_bytes();
+    else if (k == "receval") *bytes = receval_request_bytes(m, 0);
+    else if (k == "receval_rect") *bytes = receval_request_bytes(m, 1);
     else if (k == "omp") *bytes = omp_request_bytes(m);
     else if (k == "gamp") *bytes = gamp_request_bytes(m);
     else if (k == "prgamp") *bytes = prgamp_request_bytes(m);

@@ -286,6 +286,7 @@ size_t msr_request_bytes();                  // dynamic LDS of msr_kernel
 size_t hetrd_request_bytes(int d, int blk);  // ... of hetrd_kernel (blk = 0) / hetrd_blk_kernel (blk = 1)
 size_t heev2_request_bytes(int d, int which);   // ... of he2hb_kernel (0), hb2st_kernel (1), bt2_kernel (2)
 size_t scan_request_bytes();                 // ... of scan_kernel (the same at every shape)
+size_t receval_request_bytes(int N, int rect);   // ... of receval_kernel at N = max(tx, rx), square or rectangular
 size_t omp_request_bytes(int d);             // ... of omp_kernel at atom length d
 size_t gamp_request_bytes(int d);            // ... of gamp_kernel at atom length d
 size_t prgamp_request_bytes(int m);          // ... of prgamp_kernel at m measurements

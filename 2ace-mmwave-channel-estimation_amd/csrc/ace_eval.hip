@@ -50,8 +50,8 @@ namespace {
 // leaves the kernel the registers for four waves per SIMD where LDS admits them
 constexpr int EV_REG_MAX = BF_NMAX * BF_NMAX / 64, EV_REG_SMALL = 4;
 
-// Quantize_PS at 2 bits: k with k pi/2 nearest to angle(z), ties to the smaller angle (k in -2..2)
-__device__ __forceinline__ int ev_qcode(d2 z) { return (int)ceil(atan2(z.y, z.x) / kHalfPi - 0.5); }
+// Quantize_PS at 2 bits (ace_svd.hpp's ps_qcode, shared with ace_receval.hip)
+__device__ __forceinline__ int ev_qcode(d2 z) { return ps_qcode(z); }
 
 __device__ __forceinline__ d2 ev_wave_csum(d2 v) { return make_double2(wave_sum(v.x), wave_sum(v.y)); }
 

@@ -151,10 +151,27 @@ __device__ __forceinline__ void zlarfg(d2 alpha, double xnorm, double& beta, d2&
         return;
     }
     beta = -copysign(dlapy3(ar, ai, xnorm), ar);
+    if (fabs(beta) < kSafmin) {
+        // a column below the normal range (the k-th trailing block of an exactly rank-deficient matrix holds
+        // rounding noise of rounding noise, eps^k): LAPACK rescales it; here it is left alone (H = I), which
+        // moves no singular vector of a singular value that can be told from zero
+        beta = ar;
+        tau = make_double2(0.0, 0.0);
+        scal = make_double2(1.0, 0.0);
+        return;
+    }
     tau = make_double2((beta - ar) / beta, -ai / beta);
     const d2 den = make_double2(ar - beta, ai);  // zladiv(1, alpha - beta)
     const double q = den.x * den.x + den.y * den.y;
-    scal = make_double2(den.x / q, -den.y / q);
+    if (q >= kSafmin && q <= kSafmax) {
+        scal = make_double2(den.x / q, -den.y / q);
+    } else {
+        // |den|^2 leaves the range although den does not (entries near 1e-160 or 1e+160): divide scaled, as
+        // zladiv does; the branch above keeps its rounding for every other input
+        const double s = fmax(fabs(den.x), fabs(den.y));
+        const double xr = den.x / s, xi = den.y / s, q2 = xr * xr + xi * xi;
+        scal = make_double2(xr / q2 / s, -xi / q2 / s);
+    }
 }
 
 __device__ __forceinline__ d2 cconj(d2 a) { return make_double2(a.x, -a.y); }
@@ -693,6 +710,9 @@ __device__ bool gesdd_vh(const BfShared& sh, int m, int n, int ld, int lane) {
     apply_ph(sh, n, m, 0, ld, lane);
     return ok;
 }
+
+// Quantize_PS at 2 bits: k with k pi/2 nearest to angle(z), ties to the smaller angle (k in -2..2)
+__device__ __forceinline__ int ps_qcode(d2 z) { return (int)ceil(atan2(z.y, z.x) / kHalfPi - 0.5); }
 
 // z * j^k
 __device__ __forceinline__ d2 rotk(d2 z, int k) {

@@ -785,6 +785,65 @@ int ace_beam_scan_host(int batch, int d0, int d1, int Q0, int Q1, const double* 
                        const double* F1, const double* noise, int K, double* top_pow, int32_t* top_idx,
                        double* total, double* power, uint32_t* status);   /* allocates, copies, synchronous */
 
+/* ---- sparse-recovery evaluation (Evaluation_Recovery) ------------------------------------------------
+ * Numerical_Simulation/src/evaluate_plot_results/Evaluation_Recovery.m:73-338, batched against one shared pair of
+ * cut steering dictionaries: the score the reference gives PLOMP, PLGAMP, PerfectPhaseCS, NoisyPhaseCS and PRGAMP.
+ * Per call: A_t [Qt][tx], A_r [Qr][rx] c128 (the rows of the cut dictionaries; AD = kron(conj(A_t), A_r), column
+ * u Qr + v); deg_t [Qt], deg_r [Qr] f64, the grid angles in degrees (:105-113: rad2deg(asin(virtual / kappa)));
+ * first_t, first_r: the global grid index of the first cut column per side, so that column 0 is in the reference's
+ * index units; noise_power > 0; kappa = 2 pi d / lambda > 0.
+ * Per realisation: z [batch][Qt*Qr] c128; vecH [batch][tx*rx] c128 (element r + rx t); aod_deg, aoa_deg [batch][L]
+ * f64, the true angles; true_idx [batch][L][2] int32, the true paths' nearest global grid indices (AoD, AoA:
+ * Quan_Pos_Err_h_array(2, l, 1:2) of Sparse_Channel_Formulation.m:98-103; only path 0 is read, for L == 1);
+ * picks NULL or [batch][2][2] int32: (ind_F, ind_W) zero-based of pattern 1 and of pattern 2, as ace_beam_scan_batch
+ * picks them, with the tables centre_deg_t [Mt], centre_deg_r [Mr] (pattern 2's estimate and both patterns' beams:
+ * the 2-bit quantised steering vectors at the centres) and peak_deg_t [Mt], peak_deg_r [Mr] (pattern 1's estimate,
+ * ace_beam_peak_angles).  The sweep is not redone.  All DEVICE.
+ * metrics [batch][15] f64, the order of :322-336: Num_Quantization_Error, AoDA_Err, MSE_ARM, MSE_H,
+ * Rate_Unconstrained, Rate_PerCSI, Rate_Est, Rate_Est_AoDA, Rate_BSweep1, Rate_BSweep2, AoDA_Err_Sweep1,
+ * AoDA_Err_Sweep2, gain_ana, gain_dig, proj_error.  H_est [batch][tx*rx] c128 (may be NULL): AD z after the global
+ * phase of :188-189, the reference's second output.  status [batch] (may be NULL).
+ * The reference's behaviour as it stands (the L picks by modulus in ascending index order; the true AoD sorted
+ * descending while :128 leaves the true AoA unsorted; the quantisation error for L == 1 only; Num_RFchains = 1, so
+ * every beam is Quantize_PS'd at 2 bits; the AoDA beams at the LAST sorted estimate; det(eye(L) + scalar) =
+ * 1 + L |g|^2 / noise_power; columns 12-14 = Evaluation_H of (H_est, H), in ace_evaluate_batch(H_est, H, rx, tx)'s
+ * gauge) is listed in csrc/ace_receval.hip.  An exact modulus tie goes to the lower index (MATLAB: by phase angle).
+ * H_est is formed as A_r^T mat(z)^T conj(A_t) on the f64 matrix cores; z is read once.  One wavefront per realisation;
+ * a realisation's outputs are a function of its own inputs and the per-call tables alone.  Asynchronous on stream,
+ * no allocation, nothing read back, no workspace.
+ * Limits: 1 <= tx, rx <= 32, 1 <= L <= 8, 1 <= Qt, Qr <= 4096, 1 <= Mt, Mr <= 4096 (ACE_ERR_UNSUPPORTED above,
+ * ACE_ERR_ARG below); batch < 1, L > Qt Qr, a negative first index, a noise_power or kappa that is not positive and
+ * finite, a NULL required array (named in ace_last_error()) and picks without all four tables return ACE_ERR_ARG;
+ * all of it before any HIP call.  ACE_ERR_UNSUPPORTED when the kernel's dynamic LDS request is refused.
+ * Degenerate realisations (z or H not finite or all zero, an H_est that is zero or not finite, a metric that
+ * overflows): MSE_H = MSE_ARM = proj_error = 1, gains and rates 0, H_est zeros, ACE_ST_EVAL_DEGENERATE; with a
+ * degenerate z the angle columns are those of the picks 0 .. L - 1.  Without picks, or for a row with a pick outside
+ * its table (the scan's -1), columns 8-11 are NaN and ACE_ST_RECEVAL_NOSWEEP is set.  ACE_ST_BF_NOCONV as above. */
+#define ACE_ST_RECEVAL_NOSWEEP 131072u
+#define ACE_RECEVAL_NCOL 15
+int ace_evaluate_recovery_batch(int batch, int tx, int rx, int L, int Qt, int Qr, const double* A_t,
+                                const double* A_r, const double* deg_t, const double* deg_r, int first_t,
+                                int first_r, double noise_power, double kappa, const double* z, const double* vecH,
+                                const double* aod_deg, const double* aoa_deg, const int32_t* true_idx,
+                                const int32_t* picks, int Mt, int Mr, const double* centre_deg_t,
+                                const double* centre_deg_r, const double* peak_deg_t, const double* peak_deg_r,
+                                double* metrics, double* H_est, uint32_t* status, void* stream);
+int ace_evaluate_recovery_host(int batch, int tx, int rx, int L, int Qt, int Qr, const double* A_t,
+                               const double* A_r, const double* deg_t, const double* deg_r, int first_t,
+                               int first_r, double noise_power, double kappa, const double* z, const double* vecH,
+                               const double* aod_deg, const double* aoa_deg, const int32_t* true_idx,
+                               const int32_t* picks, int Mt, int Mr, const double* centre_deg_t,
+                               const double* centre_deg_r, const double* peak_deg_t, const double* peak_deg_r,
+                               double* metrics, double* H_est, uint32_t* status);   /* allocates, copies, synchronous */
+
+/* Pattern 1's angle estimate of the sweep (MyBeamSweeping.m:134-154): for each of M beams [M][N] c128 (DEVICE), the
+ * first angle of -90 : 0.005 : 90 degrees (36001 points, built from both ends as MATLAB's colon does) that maximises
+ * |f^H a(theta)|, a(theta)[k] = exp(-j kappa sin(theta) k).  peak_deg [M] f64 (DEVICE); NaN for a beam with a
+ * non-finite entry.  Once per sweep point, not per realisation.  1 <= N <= 32 (ACE_ERR_UNSUPPORTED above), M >= 1;
+ * asynchronous on stream. */
+int ace_beam_peak_angles(int M, int N, double kappa, const double* beams, double* peak_deg, void* stream);
+int ace_beam_peak_angles_host(int M, int N, double kappa, const double* beams, double* peak_deg);   /* allocates, copies, synchronous */
+
 /* ---- batched orthogonal matching pursuit (the sparse stage of PLOMP and of the coherent CS benchmark) ----
  * The reference calls OMP(C, intSoln, 1e-12) (My_TwoStage_Recovery.m) and OMP(A, y, s) (My_Conventional_CS.m);
  * OMP.m itself belongs to the external CoSaMP_OMP toolbox and is not in the reference tree.  This is textbook
@@ -1198,7 +1257,8 @@ int ace_path_counts(int64_t* counts, int reset);
 
 /* Dynamic LDS (bytes) the launcher of `kernel` requests at operand size `m` (host arithmetic, no
  * GPU call): "i8ah" (apply_AH), "i8ah_fuse", "i8ah_ky" (K Y), "gyk", "gyf", "msr", "nms" (m = the
- * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used),
+ * measurement count), "hetrd", "hetrd_blk" (m = the Hermitian order), "scan" (the beam scan; m is not used), "receval" / "receval_rect" (the recovery evaluator,
+ * square / rectangular arrays; m = max(tx, rx)),
  * "omp", "gamp" (m = d, the atoms' length), "prgamp" (m = the measurement count), "minl2" (m = the measurement count; 0 at every m).  With the kernel's static LDS
  * (compiler resource report) it must stay within the CU's 160 KiB for every shape the path takes;
  * tests/test_lds_budget.py checks that.  ACE_ERR_ARG for an unknown name. */
