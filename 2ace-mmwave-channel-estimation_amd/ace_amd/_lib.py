@@ -214,7 +214,7 @@ class UnitArgs(C.Structure):
     """Mirror of ``ace_unit_args`` (include/ace.h)."""
     _fields_ = ([(k, C.c_int32) for k in ("op", "batch", "n", "m", "it", "it_end", "maxiter", "q", "fixed_iters", "guard",
                                           "done_count", "mspcount", "lazy", "use_la", "use_ax", "yn_copy", "msp", "ctl",
-                                          "np", "msp_fail_it", "waves", "reserved")]
+                                          "np", "msp_fail_it", "waves", "state_ext")]
                 + [(k, C.c_double) for k in ("tol_rel", "tol_abs", "rho", "room", "sentinel")]
                 + [("fl", C.c_double * 4)]
                 + [(k, _dp) for k in ("A", "B") + UNIT_VM + UNIT_VN + ("state",)]
@@ -268,6 +268,8 @@ def _load():
     lib.ace_prof_stop.restype = C.c_int
     lib.ace_prof_msp_steps.argtypes = [C.POINTER(C.c_longlong)]
     lib.ace_prof_msp_steps.restype = C.c_int
+    lib.ace_recert_stats.argtypes = [ip]
+    lib.ace_recert_stats.restype = C.c_int
     lib.ace_prof_work.argtypes = [dp]
     lib.ace_prof_work.restype = C.c_int
     lib.ace_prof_work_ex.argtypes = [dp, dp, dp]

@@ -66,6 +66,7 @@ class UnitResult:
     vecw: int
     ready: np.ndarray
     guard_ok: bool
+    recert: np.ndarray = None   # [batch] int32 when the launch carried it (unit_host's recert), else None
 
     def __getattr__(self, k):
         if k in STATE:
@@ -87,9 +88,11 @@ def _ptr(x, tp=_dp):
 def unit_host(op, *, batch, n, m, A=None, it=1, it_end=0, maxiter=1 << 30, q=None, fixed_iters=False, tol_rel=1e-4,
               tol_abs=1e-8, rho=1.05, lazy=True, use_la=True, use_ax=True, yn_copy=False, msp=False, ctl=True, np_=0,
               fl=(), room=32.0, rank_one=None, msp_fail_it=-1, waves=8, guard=None, sentinel=SENTINEL, done_count=0,
-              mspcount=0, B=None, state=None, flags=None, **vecs) -> UnitResult:
+              mspcount=0, B=None, state=None, flags=None, recert=None, **vecs) -> UnitResult:
     """One launch (``ace_unit_host``).  vecs: any of VEC_M ([batch][m] complex) and VEC_N ([batch][n] complex).  q
-    defaults to the solve's (it - 1) & 1; np_, fl: the rank profile's length and shares; guard defaults to 32 rows."""
+    defaults to the solve's (it - 1) & 1; np_, fl: the rank profile's length and shares; guard defaults to 32 rows.
+    recert ([batch] or a scalar; needs ``state``): the realisations' last fresh-reference request, carried as the
+    trailing element of the state rows (``state_ext``); gyf may then raise a request, and the result has ``recert``."""
     if op not in OPS:
         raise ValueError(f"unknown op {op!r}")
     bad = set(vecs) - set(VEC_M) - set(VEC_N)
@@ -124,7 +127,14 @@ def unit_host(op, *, batch, n, m, A=None, it=1, it_end=0, maxiter=1 << 30, q=Non
         setattr(a, k, _ptr(arr(vecs.get(k), (batch, m), k)))
     for k in VEC_N:
         setattr(a, k, _ptr(arr(vecs.get(k), (batch, n), k)))
-    a.state = _ptr(arr(state, (batch, len(STATE)), "state", np.float64))
+    ext = recert is not None
+    if ext:
+        if state is None:
+            raise ValueError("recert travels with the state rows: pass state")
+        rc = np.broadcast_to(np.asarray(recert, np.float64), (batch,))
+        state = np.concatenate([np.asarray(state, np.float64).reshape(batch, len(STATE)), rc[:, None]], axis=1)
+    a.state_ext = int(ext)
+    a.state = _ptr(arr(state, (batch, len(STATE) + ext), "state", np.float64))
     a.flags = _ptr(arr(flags, (batch, len(FLAGS)), "flags", np.int32), _ip)
     a.rank_one = _ptr(arr(rank_one, (batch,), "rank_one", np.uint8), _bp)
     g = max(guard, 0)
@@ -136,7 +146,7 @@ def unit_host(op, *, batch, n, m, A=None, it=1, it_end=0, maxiter=1 << 30, q=Non
         setattr(a, k + "_out", _ptr(x))
     K, G, c = np.zeros((mz, mz), np.complex128), np.zeros((mz, mz), np.complex128), np.zeros(2)
     a.K_out, a.G_out, a.c_out = _ptr(K), _ptr(G), _ptr(c)
-    so, fo = np.zeros((bz, len(STATE))), np.zeros((bz, len(FLAGS)), np.int32)
+    so, fo = np.zeros((bz, len(STATE) + ext)), np.zeros((bz, len(FLAGS)), np.int32)
     ints = {k: np.zeros(s, np.int32) for k, s in (("done_count_out", 1), ("mspcount_out", 1), ("resume", 1),
                                                   ("steps", 4), ("vecw", 1), ("ready", 3), ("guard_ok", 1))}
     a.state_out, a.flags_out = _ptr(so), _ptr(fo, _ip)
@@ -149,7 +159,9 @@ def unit_host(op, *, batch, n, m, A=None, it=1, it_end=0, maxiter=1 << 30, q=Non
         guards[k] = x[x.size - g:].copy()
         vec[k] = body.copy().reshape(batch, m) if k == "B" else body.copy().view(np.complex128).reshape(batch, -1)
     have = op != "ready"
-    return UnitResult(vec=vec, guards=guards, state=so, flags=fo, done_count=int(ints["done_count_out"][0]),
+    rc_out = so[:, len(STATE)].astype(np.int32) if ext else None
+    so = np.ascontiguousarray(so[:, :len(STATE)])
+    return UnitResult(vec=vec, guards=guards, state=so, flags=fo, recert=rc_out, done_count=int(ints["done_count_out"][0]),
                       mspcount=int(ints["mspcount_out"][0]), K=K if have else None, G=G if have else None,
                       c=c if have else None, resume=int(ints["resume"][0]), steps=ints["steps"],
                       vecw=int(ints["vecw"][0]), ready=ints["ready"], guard_ok=bool(ints["guard_ok"][0]))

@@ -82,8 +82,15 @@ void linops_carve(Carver& cv, bool shared, int batch, int m, int n, LinOps* L) {
 //                       iteration of ace_nucmsp.hip
 //   ACE_I8_STAGES=0     the r-column stages' A V, A^H g, K Y as f64 GEMMs instead of int8 digit planes
 //   ACE_MSR=0           no m-space runs (msr_kernel): every iteration as its own launches
-//   ACE_MSR_START=<it>  first iteration at which an m-space run is tried (default 56)
-//   ACE_MSR_RETRY=<k>   after a run stopped early, the next try k iterations after its resume point
+//   ACE_MSR_START=<it>  first iteration at which an m-space run is tried (default 44; 56 with ACE_MSP_RECERT=0)
+//   ACE_MSR_RETRY=<k>   after a check that found a realisation not ready, the next one k iterations later; after a
+//                       run stopped early, the next try k iterations after its resume point (default 4; 8 with
+//                       ACE_MSP_RECERT=0)
+//   ACE_MSP_RECERT=0    an entry candidate the room test refuses never asks the Z-step for a fresh certificate
+//                       reference (RealState::recert): it waits until the stale kfcum leaves room, and the first
+//                       m-space run is tried at iteration 56 with a retry of 8, as before the rule existed
+//   ACE_RECERT_TRACE=1  the solve's fresh-reference requests, those whose exact certificate failed and the
+//                       iteration of its first m-space run on stderr and in ace_recert_stats (a host read)
 //   ACE_MSR_WAVES=4     the m-space run as four waves of four output tiles (default eight of two)
 //   ACE_TK_EIG=<it>     the one-wave Z-step takes the full profile's top-K eigenpairs by tridiagonal reduction
 //                       (topk_tri) in the init Z-step and iterations <= it; later ones run the warm Jacobi
@@ -94,10 +101,14 @@ void linops_carve(Carver& cv, bool shared, int batch, int m, int n, LinOps* L) {
 //   ACE_SETUP_OVERLAP=0 the operator setup on the caller's stream before init with a host read per flag
 //                       (default: on a side stream beside init for the unit solve on a shared A, and
 //                       two host round trips in every shared-A setup)
+// first readiness check and retry interval with the fresh-reference rule on (the bench batch's not-ready
+// count reaches 0 at iteration 42, the refinement input's by 64; measured, profiles/r08_recert_notready_trace.txt)
+constexpr int MSR_START_DEFAULT = 44, MSR_RETRY_DEFAULT = 4;
 struct Knobs {
-    int zcompact = 0, cold_sync = 0, msp_fail_it = -1, gyf_ctl = 1, msr_start = 56, msr_retry = 8, msr_waves = 8;
+    int zcompact = 0, cold_sync = 0, msp_fail_it = -1, gyf_ctl = 1, msr_waves = 8;
+    int msr_start = MSR_START_DEFAULT, msr_retry = MSR_RETRY_DEFAULT;
     int tkeig = 6;
-    bool tk_trace = false;
+    bool tk_trace = false, recert = true, recert_trace = false;
     bool msr = true;
     bool fuse = true, gyf = true, mspace = true, lazy_dual = true, lean = true, nuc_msp = true, i8r = true, zcert = true;
     bool r1lz = true;   // rank-one profile: top eigenpair by Lanczos in the one-wave Z-step (ACE_R1_LANCZOS=0: Jacobi)
@@ -131,8 +142,10 @@ static Knobs read_knobs() {
     k.r1lz = on("ACE_R1_LANCZOS");
     k.tkeig = (int)num("ACE_TK_EIG", 6);
     k.tk_trace = num("ACE_TK_TRACE", 0) != 0;
-    k.msr_start = (int)num("ACE_MSR_START", 56);
-    k.msr_retry = (int)num("ACE_MSR_RETRY", 8);
+    k.recert = on("ACE_MSP_RECERT");
+    k.recert_trace = num("ACE_RECERT_TRACE", 0) != 0;
+    k.msr_start = (int)num("ACE_MSR_START", k.recert ? MSR_START_DEFAULT : 56);
+    k.msr_retry = (int)num("ACE_MSR_RETRY", k.recert ? MSR_RETRY_DEFAULT : 8);
     if (k.msr_retry < 1) k.msr_retry = 1;
     k.msr_waves = (int)num("ACE_MSR_WAVES", 8) == 4 ? 4 : 8;
     return k;
@@ -578,6 +591,7 @@ static int admm_iterate_split(const LinOps& L, const AdmmParams& p, const AdmmSt
             int nr[3] = {0, 0, 0};
             ACE_HIP(read_back(nr, w.done + 28, sizeof(nr), st));
             run_msr = nr[0] == 0;
+            if (run_msr && kn.recert_trace && g_recert.first_run == 0) g_recert.first_run = it;
             if (msr_trace())
                 fprintf(stderr, "msr check it %d: not ready %d (not m-space %d, test pending %d)\n", it, nr[0], nr[1],
                         nr[2]);
@@ -676,7 +690,7 @@ static int admm_iterate_split(const LinOps& L, const AdmmParams& p, const AdmmSt
             GykArgs ga{L.Gf, wh.T, Bh, wh.Y[q], wh.M, wh.Y[1 - q], wh.g, wh.KY[q], wh.KY[1 - q], wh.optY,
                        L.LK8, L.c8, wh.st, wh.AX, 2 - q, L.LA8, Zc, Nc, w.zeros, n, za0.lazy_dual, dc, gyf ? 1 : 0,
                        gyf && msp ? 1 : 0, it, za.Sold, wh.Sg[it & 1], wh.optS, za0.np,
-                       {za0.fl[0], za0.fl[1], za0.fl[2], za0.fl[3]}, za.rank_one, kn.msp_room};
+                       {za0.fl[0], za0.fl[1], za0.fl[2], za0.fl[3]}, za.rank_one, kn.msp_room, kn.recert ? 1 : 0};
             if (!(pmask & 1)) {
             } else if (gyf) {
                 ProfScope ps(ACE_K_APPLY_G, sh);
@@ -804,8 +818,18 @@ static int admm_nuclear_msp(const LinOps& L, const AdmmParams& p, const AdmmStat
     return ACE_OK;
 }
 
-// ACE_TK_TRACE: the one-wave Z-step's tridiagonal uses and Jacobi fallbacks (ZArgs::tkcnt) of the solve
+// ACE_TK_TRACE: the one-wave Z-step's tridiagonal uses and Jacobi fallbacks (ZArgs::tkcnt) of the solve;
+// ACE_RECERT_TRACE: its fresh-reference requests and failed ones (ZArgs::rccnt), for ace_recert_stats too
 static int tk_report(const Knobs& kn, const AdmmState& w, int rc, hipStream_t st) {
+    if (kn.recert_trace && rc == ACE_OK) {
+        int rcc[2] = {0, 0};
+        ACE_HIP(read_back(rcc, w.done + 34, sizeof(rcc), st));
+        g_recert.requests = rcc[0];
+        g_recert.failed = rcc[1];
+        g_recert.valid = 1;
+        fprintf(stderr, "[ace] fresh-reference requests %d, exact certificate failed %d, first m-space run at %d\n", rcc[0],
+                rcc[1], g_recert.first_run);
+    }
     if (!kn.tk_trace || rc != ACE_OK) return rc;
     int tkc[2] = {0, 0};
     ACE_HIP(read_back(tkc, w.done + 32, sizeof(tkc), st));
@@ -890,6 +914,8 @@ static int admm_run_impl(const LinOps& L, LinOps* setup, const AdmmParams& p, co
     za.r1lz = kn.r1lz ? 1 : 0;
     za.tkeig = kn.tkeig > 0 ? kn.tkeig : 0;
     za.tkcnt = w.done + 32;
+    za.rccnt = w.done + 34;
+    if (kn.recert_trace) g_recert = RecertStats{};   // (diagnostics of one solve at a time: not for concurrent solves)
     za.wmode = 0;
     za.Xcur = w.V;     // wmode: X of never-improved realisations (finalize's fallback)
     za.Zn = nullptr;   // in place (init, and every kernel outside wmode)

@@ -153,6 +153,16 @@ int ace_prof_msp_steps(long long* steps) {
     return ACE_OK;
 }
 
+int ace_recert_stats(int32_t* out) {
+    g_err.clear();
+    if (!out) return fail(ACE_ERR_ARG, "out is NULL");
+    if (!g_recert.valid) return fail(ACE_ERR_ARG, "no unit solve has run under ACE_RECERT_TRACE=1");
+    out[0] = g_recert.requests;
+    out[1] = g_recert.failed;
+    out[2] = g_recert.first_run;
+    return ACE_OK;
+}
+
 int ace_prof_work(double* flops) {
     g_err.clear();
     if (!flops) return fail(ACE_ERR_ARG, "flops is NULL");

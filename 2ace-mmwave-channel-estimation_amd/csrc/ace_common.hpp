@@ -78,7 +78,11 @@ struct RealState {
     int32_t msp, mzit, z0id, msp_pad;   // msp_pad: the entry iteration it0
     // m-space run (msr_kernel) that left this realisation's block ahead of the per-iteration launches:
     // the first iteration those must run for the block (its resume point)
-    int32_t mres, mres_pad_[3];
+    // recert: the iteration at which gyk_body last asked the Z-step for a fresh certificate reference (0: never).
+    // An entry candidate whose bound has no room only because kfcum still carries the large steps since the last
+    // exact certificate asks for one: fused_control then returns 0 at that iteration, the one-wave Z-step takes the
+    // exact Ky Fan certificate on the current E (kf at E, kfcum = 0), and the entry test runs again one iteration later
+    int32_t mres, recert, mres_pad_[2];
     // A2nuclear m-space iteration (ace_nucmsp.hip): E_prev = na X_init + A^H e, Z = naz E_prev,
     // N = nbeta E_prev, nep2 = ||E_prev||^2, nx0 = ||X_init||^2; best / current iterate's X_init coefficient
     double na, nbeta, nx0, nopt_a, ncur_a, naz, nep2, npad2_;
@@ -395,7 +399,11 @@ struct GykArgs {
     double fl[4];
     const unsigned char* rank_one;
     double room;
+    // an entry candidate the room test refuses asks for a fresh certificate reference (RealState::recert) when the
+    // test would pass with kfcum = 0, at most once in RECERT_GAP + 1 iterations (ACE_MSP_RECERT; 0: never)
+    int recert;
 };
+constexpr int RECERT_GAP = 4;   // no new request within this many iterations of the last one
 void launch_gyk(int nb, int m, const GykArgs& a, hipStream_t st);
 // gyk + the fused apply_AH (Z-step pass) in one launch; needs a.lazy and a.glds
 size_t gyf_lds_bytes(int m);
@@ -581,6 +589,8 @@ struct ZArgs {
     int tkeig;             // one-wave Z-step, full profile: the top-K eigenpairs by tridiagonal reduction (topk_tri,
                            // ace_zprox1w.hip) in the init Z-step and iterations it <= tkeig (0: Jacobi throughout)
     int* tkcnt;            // (diagnostics, nullable) [2]: topk_tri uses, and fallbacks to the Jacobi eigensolver
+    int* rccnt;            // (diagnostics, nullable) [2]: fresh-reference requests (RealState::recert) the one-wave
+                           // Z-step honoured, and those whose exact certificate failed (the eigensolver ran)
 };
 // X = V + W with V = Z - N/mu, the one rounding sequence used by every producer of X in wmode
 __device__ __forceinline__ double2 xw(double2 z, double2 n, double2 w, double imu) {

@@ -65,6 +65,12 @@ struct Prof {
     long long msp_total = 0;
 };
 inline Prof g_prof;
+// the last unit solve's fresh-reference diagnostics (ace_recert_stats; requests / failed only under ACE_RECERT_TRACE):
+// requests the one-wave Z-step honoured, those whose exact certificate failed, the iteration of the first m-space run
+struct RecertStats {
+    int valid = 0, requests = 0, failed = 0, first_run = 0;
+};
+inline RecertStats g_recert;
 // solves per apply path since the last reset (ace_path_counts): 0 shared phase code (int8 digit
 // planes), 1 private phase codes (2-bit code images), 2 f64 shared A, 3 f64 private A
 inline std::atomic<long long> g_path[4];

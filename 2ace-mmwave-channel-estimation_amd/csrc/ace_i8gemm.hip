@@ -1091,12 +1091,19 @@ __device__ __forceinline__ void gyk_body(int nb, int m, const GykArgs& a, unsign
                 if (!take) {   // entry: the bound of fused_control with `room` more steps like this one
                     const bool r1 = a.rank_one && a.rank_one[j0 + t];
                     const int np = r1 ? 1 : a.np;
-                    const double cum = rs.kfcum + a.room * sqrt(s3);
+                    const double drift = a.room * sqrt(s3), cum = rs.kfcum + drift;
                     take = s0 > 0.0;
+                    bool fresh = take;   // the same test on a reference taken now (kfcum = 0)
                     for (int p = 0; p < 4 && p < np; ++p) {
                         const double fl = r1 ? 0.95 : a.fl[p], lb = rs.kf[p] * (1.0 - 1e-12) - cum;
                         take = take && lb > 0.0 && lb * lb > fl * s0 * (1.0 + 1e-9);
+                        const double lf = rs.kf[p] * (1.0 - 1e-12) - drift;
+                        fresh = fresh && lf > 0.0 && lf * lf > fl * s0 * (1.0 + 1e-9);
                     }
+                    // no room only because kfcum carries the path since the last exact certificate: ask this
+                    // iteration's Z-step for a fresh reference (RealState::recert; from this realisation's state
+                    // alone).  A fresh kf can come out below the old one, so requests are RECERT_GAP apart.
+                    if (a.recert && !take && fresh && (rs.recert == 0 || a.it - rs.recert > RECERT_GAP)) rs.recert = a.it;
                 }
                 if (take) {
                     atomicAdd(a.dc.done_count + 1, 1);   // m-space step count (ace_prof_msp_steps)

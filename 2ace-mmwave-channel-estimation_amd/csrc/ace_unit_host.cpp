@@ -69,6 +69,9 @@ int unit_run(const ace_unit_args& a) {
     if (optx && !lds_ok_budget(i8ah_budget(0), i8ah_lds_bytes(m)))
         return fail(ACE_ERR_UNSUPPORTED, "ace_unit_host (optx): apply_AH's LDS request at m = %d is refused", m);
 
+    // state_ext: the rows of state / state_out carry RealState::recert as one more trailing element, and gyf_kernel
+    // may raise the request (GykArgs::recert); 0: the rows and the launch as before the field existed
+    const size_t nstate = ACE_UNIT_NSTATE + (a.state_ext ? 1 : 0);
     const size_t g = (size_t)a.guard, bm = 2 * (size_t)batch * m, bn = 2 * (size_t)batch * n;
     const size_t mm = 2 * (size_t)m * m, mn = 2 * (size_t)m * n;
     LinOps L{};
@@ -114,7 +117,8 @@ int unit_run(const ace_unit_args& a) {
         RealState& s = rs[b];
         s.mu = 1.0;
         if (a.state) {
-            const double* v = a.state + (size_t)b * ACE_UNIT_NSTATE;
+            const double* v = a.state + (size_t)b * nstate;
+            if (a.state_ext) s.recert = (int32_t)v[ACE_UNIT_NSTATE];
             s.mu = v[0];
             s.last_res = v[1];
             s.opt_obj = v[2];
@@ -221,6 +225,7 @@ int unit_run(const ace_unit_args& a) {
     za.Snew = dS[it & 1];
     za.optS = doptS;
     za.msp_fail_it = a.msp_fail_it;
+    za.rccnt = ddone + 34;
 
     GykArgs ga{};
     ga.Gf = L.Gf;
@@ -255,6 +260,7 @@ int unit_run(const ace_unit_args& a) {
     for (int p = 0; p < 4; ++p) ga.fl[p] = a.fl[p];
     ga.rank_one = r1;
     ga.room = a.room;
+    ga.recert = a.state_ext ? 1 : 0;
 
     switch (op) {
         case ACE_UNIT_GYK: launch_gyk(batch, m, ga, st); break;
@@ -285,7 +291,8 @@ int unit_run(const ace_unit_args& a) {
     for (int b = 0; b < batch; ++b) {
         const RealState& s = rs[b];
         if (a.state_out) {
-            double* v = a.state_out + (size_t)b * ACE_UNIT_NSTATE;
+            double* v = a.state_out + (size_t)b * nstate;
+            if (a.state_ext) v[ACE_UNIT_NSTATE] = s.recert;
             v[0] = s.mu;
             v[1] = s.last_res;
             v[2] = s.opt_obj;
@@ -340,12 +347,12 @@ int unit_run(const ace_unit_args& a) {
         int ok = memcmp(&rs[batch], &rs_in[batch], sizeof(RealState)) == 0;
         for (int b = 0; b < batch && ok; ++b) {
             const RealState& s = rs[b];
-            ok = s.objcol == 0 && s.mres_pad_[0] == 0 && s.mres_pad_[1] == 0 && s.mres_pad_[2] == 0 && s.na == 0.0 &&
+            ok = s.objcol == 0 && (a.state_ext || s.recert == 0) && s.mres_pad_[0] == 0 && s.mres_pad_[1] == 0 && s.na == 0.0 &&
                  s.nbeta == 0.0 && s.nx0 == 0.0 && s.nopt_a == 0.0 && s.ncur_a == 0.0 && s.naz == 0.0 && s.nep2 == 0.0 &&
                  s.npad2_ == 0.0;
         }
         for (int k = 2; k < 64 && ok; ++k)
-            if (k != 8 && !(k >= 12 && k < 16) && !(k >= 28 && k < 31) && k != 40) ok = cnt[k] == 0;
+            if (k != 8 && !(k >= 12 && k < 16) && !(k >= 28 && k < 31) && k != 40) ok = cnt[k] == 0;   // ([34..35]: no Z-step here)
         *a.guard_ok = ok;
     }
     return ACE_OK;

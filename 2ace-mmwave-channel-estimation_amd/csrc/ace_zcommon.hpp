@@ -252,6 +252,9 @@ __device__ __forceinline__ int fused_control(const ZArgs& a, RealState* st, cons
         pass &= lb > 0.0 && lb * lb > pf.fl[p] * s0 * (1.0 + 1e-9);
     }
     pass &= !(a.msp && s.mzit == it && it == a.msp_fail_it);   // (tests: the fallback path)
+    // gyk_body asked for a fresh reference at this iteration (RealState::recert; never for a realisation in m-space
+    // form): the full Z-step takes the exact certificate on X in Z', as after a failed bound
+    pass &= s.recert != it;
     if (!pass) return 0;
     const bool improved_pre = sqrt(s.obj2) < s.opt_obj;
     const int optsrc = s.optsrc;   // (the fused kernel kept a best iterate in Z')

@@ -1237,6 +1237,10 @@ __device__ __forceinline__ void zstep1w_body(const ZArgs& a, int b) {
         st->kfcum = 0.0;
 #pragma unroll
         for (int pi = 0; pi < 4; ++pi) st->kf[pi] = kok ? kfv[pi] : 0.0;
+        if (a.rccnt && xin && st->recert == a.it) {   // (diagnostics: fresh-reference requests, failed ones)
+            atomicAdd(a.rccnt, 1);
+            if (!kok) atomicAdd(a.rccnt + 1, 1);
+        }
         if (improved_pre) optsrc = (defer_opt && pp && fast) ? zn_id : 0;
         st->optsrc = optsrc;
     }

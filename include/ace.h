@@ -621,6 +621,9 @@ int ace_pl_host(const ace_pl_args* args);
  *   done_count / mspcount (and _out): the batch's counts of stopped realisations and of m-space steps before / after
  *   guard_ok: 1 when the control block after the batch's and every control-block field not listed above are as
  *          they were
+ *   state_ext = 1: the rows of state and state_out have ACE_UNIT_NSTATE + 1 elements, the last one recert (the iteration
+ *          of the realisation's last fresh-reference request, 0: none), and gyf_kernel may raise a request as in a
+ *          solve with ACE_MSP_RECERT on; 0: the rows above, and no request is raised
  * Checked before any HIP call: ACE_ERR_ARG for an unknown op, batch, n or m < 1, a negative guard, it < 1, q not 0 / 1,
  * rho <= 0, np outside 0..4, it_end <= it or waves not 8 / 4 (MSR) and a NULL required array (named in
  * ace_last_error()); ACE_ERR_UNSUPPORTED for m > 256, for MSR at m != 256 and for a refused LDS request or a
@@ -630,7 +633,7 @@ enum { ACE_UNIT_GYK = 0, ACE_UNIT_GYF, ACE_UNIT_AHF, ACE_UNIT_MSR, ACE_UNIT_READ
 #define ACE_UNIT_NFLAG 16
 typedef struct ace_unit_args {
     int32_t op, batch, n, m, it, it_end, maxiter, q, fixed_iters, guard, done_count, mspcount;
-    int32_t lazy, use_la, use_ax, yn_copy, msp, ctl, np, msp_fail_it, waves, reserved;
+    int32_t lazy, use_la, use_ax, yn_copy, msp, ctl, np, msp_fail_it, waves, state_ext;
     double tol_rel, tol_abs, rho, room, sentinel;
     double fl[4];
     const double *A, *B, *T, *g, *Y0, *Y1, *KY0, *KY1, *M, *AX, *optY, *S0, *S1, *optS;
@@ -1237,6 +1240,11 @@ int ace_prof_stop(double* total_ms, int32_t* launches);
  * settled in m-space form (RealState::msp: no apply_AH pass, no Z traffic), for the bench's
  * per-launch work accounting. */
 int ace_prof_msp_steps(long long* steps);
+/* Fresh-reference diagnostics of the last unit solve run with ACE_RECERT_TRACE=1 in the environment: out[0] requests
+ * for a fresh certificate reference (RealState::recert) the one-wave Z-step honoured, out[1] those whose exact Ky Fan
+ * certificate failed (the eigensolver ran), out[2] the iteration at which the first m-space run started (0: none).
+ * ACE_ERR_ARG when no such solve has run.  One solve at a time: not for concurrent solves. */
+int ace_recert_stats(int32_t* out);
 /* Algorithmic flops (8 per complex multiply-add) of the launches the last ace_prof_start /
  * ace_prof_stop pair recorded, per kernel class: the GEMM-shaped applies and prox steps of the
  * f64 path (pipeline stages, PhaseLift) carry their count; classes the caller accounts for
